@@ -1,7 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- labels/s of the MI355X TEASAR hot path on BASELINE.json's workload.
 
-  python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N > 1: launched by torch.distributed.run)
+
+A plain run does only what the headline needs: it builds the volume, sets up the lanes, warms up, times the K steps, writes
+the outputs of the last timed step when --dump-outputs is given, and prints the JSON line (`value`, `ms_per_step`, ...).
+Everything else (the latency of one volume, the instrumented pass, the rooflines, the CPU baselines, the other scaling
+mode for N > 1) runs only with --full and adds the extra objects listed below to the same line.
+
+--dump-outputs DIR: the skeletons of the last timed step, ordered by label id, as float32 / float64 .npy files in DIR
+(skeleton_ids, vertex_counts, edge_counts, vertices, edges, radii, vertex_types; edges index the skeleton's own vertices).
+The inputs are deterministic, so two builds run with the same arguments can be compared file by file.  Above 64 MB in all,
+a seeded sample of the skeletons is written instead (the ids in skeleton_ids say which).
 
 One "step" = one pass of kimimaro.skeletonize's work over the synthetic label volume, which is ALREADY
 RESIDENT IN HBM: connected components (kh_ccl26) -> whole-volume EDT -> per-label statistics -> border
@@ -11,8 +21,8 @@ input are outside the timed region (`preamble_s`).
 
 N > 1 (default --scaling strong = BASELINE.json configs[3]): ONE volume, its connected components dealt over the ranks
 (largest first to the least loaded rank, kimimaro_amd.intake.shard_components), every rank recomputes the whole-volume
-preamble, the skeletons are all-gathered; value = components of the volume / max-over-ranks step time.  The same run
-then measures the weak mode as well (every rank its own volume of the workload's size: rank 0's volume mirrored along
+preamble, the skeletons are all-gathered; value = components of the volume / max-over-ranks step time.  With --full the
+same run then measures the weak mode as well (every rank its own volume of the workload's size: rank 0's volume mirrored along
 the axes given by the bits of r, label ids offset) and prints it as the extra object "weak_scaling".
 
 Workload (config.workload): "c3" = 512x512x512, 2124 chains, anisotropy (16,16,40), default
@@ -28,10 +38,11 @@ more than fill the rounds of the run evenly): the wall clock of ONE volume is th
 for seconds while the rest of the GPU idles.  The K timed steps are therefore issued from F lanes (host threads by
 default, --lanes process for processes), each with a HIP stream, an Engine and scratch of its own and one wave per label in its path
 loop, so that the tail of one volume overlaps the next ones; every step still does all of its work inside the timed region and
-ms_per_step = wall / K.  The latency of a single volume on an otherwise idle GPU is measured in the same run (untimed, on the default
-engine: what kimimaro_amd.skeletonize() does) and printed as single_volume_ms; --inflight 1 times the steps one after the other.
+ms_per_step = wall / K.  With --full (or when the lanes are staggered, which needs it) the latency of a single volume on an otherwise
+idle GPU is measured in the same run (untimed, on the default engine: what kimimaro_amd.skeletonize() does) and printed as
+single_volume_ms; --inflight 1 times the steps one after the other.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      the DOMINANT kernel, trace_paths_kernel (97 % of the GPU time): SURVEY 8d per-label algorithmic bytes of one
                 volume / the longest of the volume's (overlapped) path-loop launches, HIP events on each launch's own stream;
                 `traffic` from the newest committed rocprofv3 --pmc pass (marked STALE when it predates this round's kernels).
@@ -60,8 +71,10 @@ import time
 import numpy as np
 
 # one hardware queue per lane stream (up to 12 lanes + RCCL): with the default of 4, a fifth stream shares a queue and its kernels wait for the
-# seconds-long path kernel queued before them (profiles/r02b_inflight_timeline.txt)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+# seconds-long path kernel queued before them (profiles/r02b_inflight_timeline.txt).  A smaller value inherited from the
+# environment is raised: kimimaro_amd.lanes refuses to run twenty lanes on four queues once the runtime has started.
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").strip().isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 32:
+    os.environ["GPU_MAX_HW_QUEUES"] = "32"
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -81,9 +94,63 @@ WORKLOADS = {
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
-def make_volume(name):
+def _nearest_labels_blocked(tree, pts, lab_of_point, shape, anf, device, block=8):
+    """the label of the nearest point for every voxel, as make_volume's per-slab KD-tree queries give it, but blocked: the KD-tree
+    only lists candidates for each block of block^3 voxels (every point within d(centre, nearest) + 2 * half-diagonal of the
+    block centre, which holds each voxel's nearest point), and the candidates are ranked on `device` with the same float64
+    squared distances.  A uint32 volume in F order."""
+    import torch
+    nb = [-(-s // block) for s in shape]
+    lo = np.stack(np.meshgrid(*[np.arange(n) * block for n in nb], indexing="ij"), -1).reshape(-1, 3)
+    hi = np.minimum(lo + block - 1, np.asarray(shape) - 1)
+    centre = (lo + hi) / 2.0 * anf
+    half = np.sqrt(((((hi - lo) / 2.0) * anf) ** 2).sum(1))
+    dc, _ = tree.query(centre, workers=-1)
+    bound = (dc + 2.0 * half) * (1.0 + 1e-9) + 1e-6
+    off = torch.stack(torch.meshgrid(*[torch.arange(block, device=device)] * 3, indexing="ij"), -1).reshape(1, -1, 3)
+    P = torch.as_tensor(pts, dtype=torch.float64, device=device)
+    A = torch.as_tensor(anf, dtype=torch.float64, device=device)
+    L = torch.as_tensor(lab_of_point.astype(np.int64), device=device)
+    LO = torch.as_tensor(lo, device=device)
+    out = torch.empty((lo.shape[0], block ** 3), dtype=torch.int64, device=device)
+    todo = np.arange(lo.shape[0])
+    k = 48
+    while todo.size:
+        k = min(k, pts.shape[0])
+        d, cand = tree.query(centre[todo], k=k, workers=-1)
+        d, cand = d.reshape(todo.size, k), cand.reshape(todo.size, k)
+        whole = (d[:, -1] > bound[todo]) | (k == pts.shape[0])    # every point within the bound is among the k nearest
+        sel = todo[whole]
+        cand = cand[whole]
+        per = max(1, int(2e8 // (block ** 3 * k * 8)))
+        for s in range(0, sel.size, per):
+            b = torch.as_tensor(sel[s:s + per], device=device)
+            c = torch.as_tensor(cand[s:s + per], device=device)
+            V = (LO[b][:, None, :] + off).to(torch.float64) * A                                       # (n, block^3, 3)
+            Q = P[c]                                                                                     # (n, k, 3)
+            t = V[:, :, None, 0] - Q[:, None, :, 0]
+            d2 = t * t
+            t = V[:, :, None, 1] - Q[:, None, :, 1]
+            d2 = d2 + t * t
+            t = V[:, :, None, 2] - Q[:, None, :, 2]
+            d2 = d2 + t * t
+            out[b] = L[c.gather(1, d2.argmin(2))]
+            del V, Q, t, d2
+        todo = todo[~whole]
+        k *= 4
+    vol = out.reshape(nb[0], nb[1], nb[2], block, block, block).permute(2, 5, 1, 4, 0, 3)
+    vol = vol.reshape(nb[2] * block, nb[1] * block, nb[0] * block)[:shape[2], :shape[1], :shape[0]]
+    lab = vol.to(torch.int32).contiguous().cpu().numpy().view(np.uint32).T            # (z, y, x) C order = (x, y, z) F order
+    del out, vol, P, L, LO
+    if str(device).startswith("cuda"):
+        torch.cuda.empty_cache()
+    return lab
+
+
+def make_volume(name, device=None):
     """SURVEY.md 8d recipe: dense 'neurite' tessellation = nearest chain point under the anisotropic
-    metric, label ids 1000 + perm(i).  Deterministic (np.random.default_rng(seed))."""
+    metric, label ids 1000 + perm(i).  Deterministic (np.random.default_rng(seed)).  `device`: rank the nearest points there
+    (_nearest_labels_blocked, the same volume in a fraction of the time) instead of one KD-tree query per voxel."""
     from scipy.spatial import cKDTree
     shape, nchains, npts, seed, an = WORKLOADS[name]
     cache = os.environ.get("KIMI_VOLUME_CACHE")     # developer knob: keep the generated volume between runs on one box
@@ -106,16 +173,20 @@ def make_volume(name):
             d = rng.normal(size=3)
             d /= np.linalg.norm(d) + 1e-9
             p = np.clip(p + step * d, 0, shp - 1)
-    tree = cKDTree(np.asarray(pts) * anf)
+    pts = np.asarray(pts) * anf
+    tree = cKDTree(pts)
     ids = (1000 + rng.permutation(nchains)).astype(np.uint32)
     owner = np.asarray(owner)
-    lab = np.empty(shape, dtype=np.uint32, order="F")
     gx, gy = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), indexing="ij")
-    base = np.stack([gx.ravel(order="F") * anf[0], gy.ravel(order="F") * anf[1]], axis=1)
-    for z in range(shape[2]):  # per slab: bounded host memory
-        q = np.concatenate([base, np.full((base.shape[0], 1), z * anf[2])], axis=1)
-        _, idx = tree.query(q, workers=-1)
-        lab[:, :, z] = ids[owner[idx]].reshape(shape[0], shape[1], order="F")
+    if device is not None:
+        lab = _nearest_labels_blocked(tree, pts, ids[owner], shape, anf, device)
+    else:
+        lab = np.empty(shape, dtype=np.uint32, order="F")
+        base = np.stack([gx.ravel(order="F") * anf[0], gy.ravel(order="F") * anf[1]], axis=1)
+        for z in range(shape[2]):  # per slab: bounded host memory
+            q = np.concatenate([base, np.full((base.shape[0], 1), z * anf[2])], axis=1)
+            _, idx = tree.query(q, workers=-1)
+            lab[:, :, z] = ids[owner[idx]].reshape(shape[0], shape[1], order="F")
     if name in ("c2soma", "c2soma2"):
         centres = [(shp - 1) / 2.0] if name == "c2soma" else [(shp - 1) / 2.0 - np.array([128.0, 0, 0]), (shp - 1) / 2.0 + np.array([128.0, 0, 0])]
         gz = np.arange(shape[2])
@@ -257,6 +328,39 @@ def _lane_step(st, eng, payload):
     return volume_step(eng, st)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(skels, outdir):
+    """--dump-outputs: the skeletons {label: Skeleton} of one step as float32 / float64 arrays, ordered by label id.  Above
+    DUMP_LIMIT_BYTES a seeded sample of the skeletons is kept (whole skeletons, still in label order)."""
+    ids = sorted(skels)
+    per = [skels[i].vertices.shape[0] * (3 * 4 + 4 + 4) + skels[i].edges.shape[0] * 2 * 8 + 3 * 8 for i in ids]
+    if sum(per) > DUMP_LIMIT_BYTES:
+        order = np.random.default_rng(0).permutation(len(ids))
+        keep, total = [], 0
+        for j in order:
+            if total + per[j] > DUMP_LIMIT_BYTES:
+                continue
+            keep.append(j)
+            total += per[j]
+        ids = [ids[j] for j in sorted(keep)]
+    sk = [skels[i] for i in ids]
+    arrays = {
+        "skeleton_ids": np.asarray(ids, dtype=np.float64),
+        "vertex_counts": np.asarray([s.vertices.shape[0] for s in sk], dtype=np.float64),
+        "edge_counts": np.asarray([s.edges.shape[0] for s in sk], dtype=np.float64),
+        "vertices": np.concatenate([s.vertices for s in sk] or [np.zeros((0, 3))]).astype(np.float32).reshape(-1, 3),
+        "edges": np.concatenate([s.edges for s in sk] or [np.zeros((0, 2))]).astype(np.float64).reshape(-1, 2),
+        "radii": np.concatenate([s.radii for s in sk] or [np.zeros(0)]).astype(np.float32),
+        "vertex_types": np.concatenate([s.vertex_types for s in sk] or [np.zeros(0)]).astype(np.float32),
+    }
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return len(ids)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -279,7 +383,12 @@ def main():
                     help="N > 1: strong (default, BASELINE.json configs[3]) = ONE volume, its components dealt over the GPUs "
                          "(largest first to the least loaded rank); weak = every GPU skeletonizes its own volume of the "
                          "workload's size (a mirrored copy with its own label ids).  The mode that is not selected is "
-                         "measured as well (fewer steps) and printed as an extra object.")
+                         "measured as well (fewer steps, --full only) and printed as an extra object.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the latency of one volume, the instrumented pass "
+                         "(phases, sweep, chains), the rooflines, the CPU baselines and (N > 1) the other scaling mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the skeletons of the last timed step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     import torch
@@ -316,7 +425,7 @@ def main():
         shape0, _, _, _, an = WORKLOADS[args.workload]
         try:
             if rank == 0:
-                base_lab, an = make_volume(args.workload)
+                base_lab, an = make_volume(args.workload, device=eng.device)
                 d_vol = eng.to_device(base_lab)
             else:
                 d_vol = torch.empty(int(np.prod(shape0)), dtype=torch.int32, device=eng.device)
@@ -328,7 +437,7 @@ def main():
             print("bench: broadcast of the volume failed (%r); generating locally" % (e,), file=sys.stderr)
             base_lab, an = make_volume(args.workload)
     else:
-        base_lab, an = make_volume(args.workload)
+        base_lab, an = make_volume(args.workload, device=eng.device)
     an = np.asarray(an, dtype=np.float32)
     params = dict(kimimaro_amd.DEFAULT_TEASAR_PARAMS)
     dust = 1000
@@ -403,7 +512,7 @@ def main():
         rounds = -(-max(args.steps, 1) // most)
         return int(-(-max(args.steps, 1) // rounds))
 
-    widths = {m: width_of(m) for m in (("weak", "strong") if world > 1 else (args.scaling,))}
+    widths = {m: width_of(m) for m in (("weak", "strong") if world > 1 and args.full else (args.scaling,))}
     if dist:
         # every rank must run the same number of fill steps (each ends in the gather collective): the ranks agree on the
         # smallest lane count any of them came up with from its own free memory
@@ -431,11 +540,14 @@ def main():
                 os.remove(state["shm"])
             state["shm"] = None
 
+    def stagger_on(n, width):
+        """whether a run of n steps on `width` lanes offsets the lanes' first jobs (by single_ms / width, see run_steps)"""
+        want = os.environ.get("KIMI_BENCH_STAGGER")
+        return (n >= 4 * width) if want is None else (want == "1" and n > width)
+
     def run_steps(n, width):
         if plane["obj"] is not None and width > 1:
-            want = os.environ.get("KIMI_BENCH_STAGGER")
-            on = (n >= 4 * width) if want is None else (want == "1" and n > width)
-            stagger = state.get("single_ms", 0.0) / 1e3 / width if on else 0.0
+            stagger = state.get("single_ms", 0.0) / 1e3 / width if stagger_on(n, width) else 0.0
             for _, local in plane["obj"].run(_lane_step, [None] * n, width=width, stagger=stagger):
                 finish(local)
             return
@@ -446,9 +558,7 @@ def main():
         # lanes offset by latency / width, so that the GPU-filling part of one volume meets the tails of the others instead
         # of the other lanes' GPU-filling parts: measured +2.3 % over 20 steps, -3 % over 8 (the ramp costs more than the
         # interleaving wins), hence only for long runs.  KIMI_BENCH_STAGGER=0 / 1 forces it off / on.
-        want = os.environ.get("KIMI_BENCH_STAGGER")
-        on = (n >= 4 * width) if want is None else (want == "1" and n > width)
-        stagger = state.get("single_ms", 0.0) / 1e3 / width if on else 0.0
+        stagger = state.get("single_ms", 0.0) / 1e3 / width if stagger_on(n, width) else 0.0
         if os.environ.get("KIMI_BENCH_STAGGER_S"):           # developer knob: seconds between the lanes' first jobs
             stagger = float(os.environ["KIMI_BENCH_STAGGER_S"]) if n > width else 0.0
         for _, local in lanes.run(lambda e, k: local_step(e), n, width=width, stagger=stagger):
@@ -457,7 +567,7 @@ def main():
     def measure(mode, warmup, steps, latency=True):
         width = widths[mode]
         torch.cuda.empty_cache()           # scratch of the other mode / of the preparation goes back to the device
-        if latency:
+        if latency or (width > 1 and any(stagger_on(n, width) for n in (warmup, steps))):   # (the stagger needs single_ms)
             # one volume alone on an otherwise idle GPU, the way kimimaro_amd.skeletonize() runs it (default engine: 256 threads
             # per label, the largest labels on a second stream): its latency, untimed; twice, the first call fills the pool
             eng.time_kernels = True        # HIP events around the path-loop launches of these PRODUCTION calls (-> roofline)
@@ -512,7 +622,7 @@ def main():
 
     # the other scaling mode first (short), the selected one last so that everything below describes the selected one
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         omode = "weak" if args.scaling == "strong" else "strong"
         prepare(omode)
         osteps = max(1, min(args.steps, 4))
@@ -523,13 +633,14 @@ def main():
         other = {"mode": omode, "elapsed": oel, "steps": osteps, "skeletons": len(result["skels"])}
     preamble_s = prepare(args.scaling)
     try:
-        elapsed = measure(args.scaling, args.warmup, args.steps)
+        elapsed = measure(args.scaling, args.warmup, args.steps, latency=args.full)
     finally:
         close_process_lanes()              # (their HBM goes back before the instrumented pass of this process)
+    last_skels = result["skels"]           # what the last timed step returned (--dump-outputs)
     # what the lanes' last volumes looked like UNDER LOAD (thread lanes: the engines are still there): the longest chain of
     # each and the cycle sums, to be read against the solo pass below (`chains`)
     loaded = None
-    if lanes is not None:
+    if lanes is not None and args.full:
         loaded = []
         for e_ in lanes.engines:
             lt = e_.last_tasks
@@ -548,7 +659,7 @@ def main():
     ieng = lanes.engines[0] if lanes is not None else eng
     timings = []
     tk = None
-    if rank == 0:
+    if rank == 0 and args.full:
         with (lanes._scopes[0] if lanes is not None else contextlib.nullcontext()):
             torch.cuda.synchronize()
             t_ccl = time.perf_counter()
@@ -590,6 +701,48 @@ def main():
         if dist:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(last_skels, args.dump_outputs)
+
+    line = {
+        "metric": "labels/sec on a dense connectomics-shaped volume (skeletonize hot path, labels resident in HBM)",
+        "value": round(value, 3), "unit": "labels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling,
+        "volumes_in_flight": inflight,
+        "hbm_reserved_peak_gb": round((torch.cuda.max_memory_reserved() + plane["peak"]) / 1e9, 1),
+        "hbm_free_when_lanes_were_chosen_gb": state.get("hbm_free_gb"),
+        "daf_tie_note": _daf_tie_note(args.workload),
+        "lanes": args.lanes if inflight > 1 else "none",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%s: %dx%dx%d uint32, %d chains -> %d components > dust, anisotropy=%s, "
+                               "default teasar_params, fix_branching=True, fix_borders=%s, dust_threshold=%d"
+                               % (args.workload, shape[0], shape[1], shape[2], WORKLOADS[args.workload][1], ncomp,
+                                  tuple(float(a) for a in an), fix_borders, dust),
+                   "parallelism": ("one such volume per GPU (mirrored copies, own label ids) on %d GPU(s), no data-path "
+                                   "collective, skeleton all-gather-v at the end" % world) if args.scaling == "weak" else
+                                  ("components of ONE volume dealt over %d GPU(s) (largest first to the least loaded rank), "
+                                   "skeleton all-gather-v" % world),
+                   "volumes_in_flight": inflight},
+        "skeletons": nskel, "labels_per_s_by_label_count": round(nskel * (world if args.scaling == "weak" else 1) / (ms_per_step / 1e3), 3),
+        "preamble_s": round(preamble_s, 3), "phases_under_load": state.get("phases_under_load"),
+    }
+    if state.get("rank_times"):
+        line["rank_times"] = state["rank_times"]
+    if args.full:
+        line.update(full_measurements(args, eng, _abi, components, state, shape, an, params, dust, ncomp, value, inflight,
+                                      cc_labels, remapping, world, t_ccl, timings, tk, loaded))
+        line["hbm_reserved_peak_gb"] = round((torch.cuda.max_memory_reserved() + plane["peak"]) / 1e9, 1)   # (incl. the extras)
+    if other is not None:
+        line["weak_scaling" if other["scaling"] == "weak" else "strong_scaling"] = other
+    print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, eng, _abi, components, state, shape, an, params, dust, ncomp, value, inflight, cc_labels,
+                      remapping, world, t_ccl, timings, tk, loaded):
+    """--full: the extra objects of the JSON line (rooflines, instrumented pass, CPU baselines, like-for-like ratios)"""
+    import torch
 
     # ---- roofline of the EDT pass kernels: HIP events on the launch stream (kh_edt_timed)
     import ctypes as C
@@ -737,29 +890,11 @@ def main():
     if cpu_all and cpu_all.get("throughput") and cpu_all["throughput"].get("value") and world == 1:
         speedup_throughput = round(value / cpu_all["throughput"]["value"], 2)
 
-    line = {
-        "metric": "labels/sec on a dense connectomics-shaped volume (skeletonize hot path, labels resident in HBM)",
-        "value": round(value, 3), "unit": "labels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": args.scaling,
-        "volumes_in_flight": inflight, "single_volume_ms": round(state.get("single_ms", float("nan")), 3),
+    single_ms = state.get("single_ms", float("nan"))
+    return {
+        "single_volume_ms": round(single_ms, 3),
         "value_single_volume": round(ncomp / (single_ms / 1e3), 3) if single_ms == single_ms else None,
-        "hbm_reserved_peak_gb": round((torch.cuda.max_memory_reserved() + plane["peak"]) / 1e9, 1),
-        "hbm_free_when_lanes_were_chosen_gb": state.get("hbm_free_gb"),
-        "daf_tie_note": _daf_tie_note(args.workload),
-        "lanes": args.lanes if inflight > 1 else "none",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "%s: %dx%dx%d uint32, %d chains -> %d components > dust, anisotropy=%s, "
-                               "default teasar_params, fix_branching=True, fix_borders=%s, dust_threshold=%d"
-                               % (args.workload, shape[0], shape[1], shape[2], WORKLOADS[args.workload][1], ncomp,
-                                  tuple(float(a) for a in an), fix_borders, dust),
-                   "parallelism": ("one such volume per GPU (mirrored copies, own label ids) on %d GPU(s), no data-path "
-                                   "collective, skeleton all-gather-v at the end" % world) if args.scaling == "weak" else
-                                  ("components of ONE volume dealt over %d GPU(s) (largest first to the least loaded rank), "
-                                   "skeleton all-gather-v" % world),
-                   "volumes_in_flight": inflight},
-        "skeletons": nskel, "labels_per_s_by_label_count": round(nskel * (world if args.scaling == "weak" else 1) / (ms_per_step / 1e3), 3),
-        "preamble_s": round(preamble_s, 3), "phases_s": phases, "sweep": sweep, "chains": chain_info, "chains_under_load": loaded,
-        "phases_under_load": state.get("phases_under_load"),
+        "phases_s": phases, "sweep": sweep, "chains": chain_info, "chains_under_load": loaded,
         "roofline": roofline, "roofline_edt": roofline_edt, "cpu_baseline": cpu,
         "cpu_baseline_all_cores": cpu_all,
         "speedup_latency": speedup_latency, "speedup_throughput": speedup_throughput,
@@ -768,13 +903,6 @@ def main():
                         "pool is saturated from one volume on, 245 / 248 / 247 components/s for 1 / 4 / 8 volumes)"
                         % (inflight, min(inflight, 4)),
     }
-    if state.get("rank_times"):
-        line["rank_times"] = state["rank_times"]
-    if other is not None:
-        line["weak_scaling" if other["scaling"] == "weak" else "strong_scaling"] = other
-    print(json.dumps(line))
-    if dist:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -27,7 +27,7 @@ def test_bench_two_ranks_gloo_dry_run():
     env = dict(os.environ, KIMI_BENCH_BACKEND="gloo", KIMI_BENCH_INFLIGHT="2", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0",
-           "--workload", "mini", "--no-cpu-baseline"]
+           "--workload", "mini", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

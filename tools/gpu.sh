@@ -72,13 +72,13 @@ for STEP in "$@"; do
     full)
       timeout 1800 python -m pytest tests -q -m gpu > $OUT/full.txt 2>&1; echo "rc=$?"; tail -6 $OUT/full.txt ;;
     single)
-      ( envs "${A2:-}"; KIMI_BENCH_DUMP_TASKS=$OUT/${A1}_tasks.npz KIMI_BENCH_INFLIGHT=1 timeout 900 python bench.py --workload c3 --steps 2 --warmup 0 --no-cpu-baseline > $OUT/$A1.json 2> $OUT/$A1.err )
+      ( envs "${A2:-}"; KIMI_BENCH_DUMP_TASKS=$OUT/${A1}_tasks.npz KIMI_BENCH_INFLIGHT=1 timeout 900 python bench.py --full --workload c3 --steps 2 --warmup 0 --no-cpu-baseline > $OUT/$A1.json 2> $OUT/$A1.err )
       summary $OUT/$A1.json $A1 ;;
     lanes)
-      ( envs "${A4:-}"; timeout 1500 python bench.py --steps $A2 --warmup $A3 --no-cpu-baseline > $OUT/$A1.json 2> $OUT/$A1.err )
+      ( envs "${A4:-}"; timeout 1500 python bench.py --full --steps $A2 --warmup $A3 --no-cpu-baseline > $OUT/$A1.json 2> $OUT/$A1.err )
       summary $OUT/$A1.json $A1 ;;
     bench)
-      ( envs "${A3:-}"; timeout 1500 python bench.py $(echo $A2 | tr ',' ' ') > $OUT/$A1.json 2> $OUT/$A1.err )
+      ( envs "${A3:-}"; timeout 1500 python bench.py --full $(echo $A2 | tr ',' ' ') > $OUT/$A1.json 2> $OUT/$A1.err )
       summary $OUT/$A1.json $A1 ;;
     pmc)
       mkdir -p $REPO/gpurun_out/prof_$A1
@@ -93,12 +93,12 @@ for STEP in "$@"; do
     kstats)
       ( envs "${A2:-}"; cd /tmp && export TMPDIR=/tmp
         rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kstats_$A1 -o kt -- \
-          python $REPO/bench.py --steps 1 --warmup 0 --inflight 1 --no-cpu-baseline > $OUT/kstats_$A1.json 2> $OUT/kstats_$A1.err )
+          python $REPO/bench.py --full --steps 1 --warmup 0 --inflight 1 --no-cpu-baseline > $OUT/kstats_$A1.json 2> $OUT/kstats_$A1.err )
       find $OUT/kstats_$A1 -name "*kernel_stats.csv" | head -1 | xargs -r head -8 ;;
     ktrace)  # ktrace:<name>:<bench args with , for spaces>[:ENV]   kernel timeline of a bench call (rocprofv3 --kernel-trace)
       ( envs "${A3:-}"; cd /tmp && export TMPDIR=/tmp
         rocprofv3 --kernel-trace --output-format csv -d $OUT/ktrace_$A1 -o kt -- \
-          python $REPO/bench.py $(echo $A2 | tr ',' ' ') --no-cpu-baseline > $OUT/ktrace_$A1.json 2> $OUT/ktrace_$A1.err )
+          python $REPO/bench.py --full $(echo $A2 | tr ',' ' ') --no-cpu-baseline > $OUT/ktrace_$A1.json 2> $OUT/ktrace_$A1.err )
       python tools/summarize_timeline.py $(find $OUT/ktrace_$A1 -name "*kernel_trace.csv" | head -1) ;;
     probe)   # probe:<name>:<threads>[:ENV]  cycles per phase of the sweep's level loop (a -DKH_SWEEP_PROBE build given by LIB=)
       ( envs "${A3:-}"; KH_TRACE_THREADS=${A2:-64} timeout 600 python tools/trace_only.py c3 > $OUT/probe_$A1.txt 2>&1 )
