@@ -403,6 +403,38 @@ int kh_fill_voids(const uint8_t* mask, int64_t sx, int64_t sy, int64_t sz, uint3
 int kh_fill_voids_nd(const uint8_t* mask, int ndim, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint8_t* open,
                      uint8_t* out, int64_t* filled, void* stream);
 
+/* ---- kimimaro.oversegment (kimimaro/utility.py:562-644) / dijkstra3d.euclidean_distance_field(..., return_feature_map=True) from
+ * MANY sources: the geodesic Voronoi diagram of seed voxels inside every label, over the whole volume at once (csrc/feature.hip,
+ * DESIGN.md 3.10).  PARITY UNPINNED (dijkstra3d and fastremap are absent from the reference tree); the result is defined order free:
+ *   d(v) = the unique fixpoint of  d(v) = min(0 if v is a seed, min over same-label 26-neighbours u of fl(d(u) + w(u, v)))  in f32,
+ *          w as in kh_edf_batch (make_geometry); +inf where no seed reaches;
+ *   f(v) = at a seed the smallest number seeded there, elsewhere min f(u) over the neighbours u with fl(d(u) + w(u, v)) == d(v).
+ * nbrmask: the words of kh_neighbor_mask.  All volumes < 2^32 voxels, numbers 1 .. 2^32 - 2.
+ * kh_geodesic_seed: dist = +inf and feature = 0xFFFFFFFF ("none") for all nvox voxels, then for every seed s whose voxel
+ *   seed_voxel[s] carries the label seed_label[s] (!= 0): dist = 0, feature = min(feature, seed_number[s]).
+ * kh_geodesic_relax / kh_feature_relax: `sweeps` pull sweeps in place, each a launch of its own on `stream`; a sweep visits a brick
+ *   of KH_BRICK_X x KH_BRICK_Y x KH_BRICK_Z voxels only if it or one of its 26 brick neighbours changed in the sweep before.
+ *   brick_dirty: 3 planes of one byte per brick (x fastest), used round robin -- sweep number s reads plane s % 3, writes plane
+ *   (s + 1) % 3 and clears plane (s + 2) % 3; before the first sweep of a phase the caller sets plane first_sweep % 3 to 1 and the
+ *   other two to 0, and passes first_sweep = the number of sweeps of the phase already run.  changed: device u32 [2 * sweeps], set by
+ *   the call: [2 j] = bricks that changed in the call's sweep j, [2 j + 1] = bricks it visited.  The phase is at its fixpoint when
+ *   a sweep changed nothing -- the only valid end of the loop; the caller reads `changed` once per call.
+ *   kh_feature_relax must run on the FINAL dist (it does not write it).
+ * kh_first_appearance: first_of_number[n] (u32 [nnumbers + 1], set by the call) = smallest linear index whose feature is n,
+ *   0xFFFFFFFF when n owns no voxel; features 0 and > nnumbers are ignored.
+ * kh_remap_u32: feature[v] = map[feature[v]] (map: u32 [nnumbers + 1]); features 0 and > nnumbers (the "none" word) become 0.   */
+#define KH_BRICK_X 64
+#define KH_BRICK_Y 4
+#define KH_BRICK_Z 4
+int kh_geodesic_seed(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels, int label_bytes,
+                     const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature, void* stream);
+int kh_geodesic_relax(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, float* dist,
+                      uint8_t* brick_dirty, uint32_t* changed, int sweeps, int64_t first_sweep, void* stream);
+int kh_feature_relax(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz, const float* dist,
+                     uint32_t* feature, uint8_t* brick_dirty, uint32_t* changed, int sweeps, int64_t first_sweep, void* stream);
+int kh_first_appearance(const uint32_t* feature, int64_t nvox, int64_t nnumbers, uint32_t* first_of_number, void* stream);
+int kh_remap_u32(uint32_t* feature, const uint32_t* map, int64_t nnumbers, int64_t nvox, void* stream);
+
 /* ---- kh_ccl26 on HOST memory (used for the 2-D faces of fix_borders and as a cross-check),
  * restating cc3d.connected_components as called at kimimaro/utility.py:74-77.
  * Returns the number of components (ids 1..N by first appearance in F-order raster).   */

@@ -14,5 +14,6 @@ from .intake import DEFAULT_TEASAR_PARAMS, DimensionError, skeletonize  # noqa: 
 from .lanes import skeletonize_many  # noqa: F401
 from .post import join_close_components, postprocess  # noqa: F401
 from .skeleton import Skeleton  # noqa: F401
+from .utility import oversegment  # noqa: F401
 
 __version__ = "0.1.0"

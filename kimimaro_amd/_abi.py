@@ -20,6 +20,7 @@ SYMBOLS = [
     "kh_neighbor_mask", "kh_apply_voxel_graph", "kh_edf_batch", "kh_pdrf", "kh_trace_paths", "kh_fill_f32", "kh_fill_u8",
     "kh_gather_f32", "kh_init_alive", "kh_level_keys", "kh_invalidate_cube", "kh_invalidate_ball", "kh_path_search", "kh_parental_field", "kh_path_from_parents", "kh_zero2inf", "kh_inf2zero", "kh_pdrf_field", "kh_target_max", "kh_find_target", "kh_first_label", "kh_ccl26", "kh_ccl26_graph", "kh_edt_graph_cells", "kh_edt_graph_sample", "kh_fill_voids", "kh_fill_voids_nd", "kh_host_ccl26", "kh_host_find_border_targets", "kh_host_merge_components",
     "kh_host_consolidate_paths",
+    "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
 ]
 
 
@@ -52,6 +53,8 @@ SWEEP_LDS_LEVELS = 16384  # KH_SWEEP_LDS_LEVELS
 SWEEP_MAX_LEVELS = 1 << 22  # labels with more levels than this use the heap emulation only
 PDRF_BASE, PDRF_FINISH = -1, -2  # KH_PDRF_BASE / KH_PDRF_FINISH
 PDRF_KEEP_OTHERS = 0x100         # KH_PDRF_KEEP_OTHERS
+BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of kh_geodesic_relax / kh_feature_relax
+NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
 
 
 def is_pow2_exponent(e):
@@ -142,6 +145,11 @@ def lib():
     L.kh_host_merge_components.restype = i64
     L.kh_host_consolidate_paths.argtypes = [i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
     L.kh_host_consolidate_paths.restype = i64
+    L.kh_geodesic_seed.argtypes = [vp, vp, i64, vp, ci, vp, i64, vp, vp, vp]
+    L.kh_geodesic_relax.argtypes = [vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, ci, i64, vp]
+    L.kh_feature_relax.argtypes = [vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, ci, i64, vp]
+    L.kh_first_appearance.argtypes = [vp, i64, i64, vp, vp]
+    L.kh_remap_u32.argtypes = [vp, vp, i64, i64, vp]
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error",

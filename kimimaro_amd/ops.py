@@ -196,10 +196,49 @@ def compute_pdrf(dbf_max, pdrf_scale, pdrf_exponent, DBF, DAF, max_daf):
     return d_out.cpu().numpy().reshape(np.asarray(DBF).shape, order="F")
 
 
+def _edf_many_sources(labels, sources, anisotropy, return_max_location, return_feature_map):
+    """euclidean_distance_field from several sources at once, as kimimaro/utility.py:613-617 calls it: the whole-volume relaxation
+    of kimimaro_amd.feature (csrc/feature.hip) on the mask; feature_map = 1-based number of the nearest source (the smallest among
+    equally far ones), 0 where the field is +inf."""
+    from . import feature
+    eng = engine()
+    lab = _f3(labels)
+    shape = tuple(int(v) for v in lab.shape)
+    src = np.asarray(sources, dtype=np.int64).reshape(-1, 3)
+    if src.shape[0] >= 2 ** 32 - 2:
+        raise ValueError("fewer than 2^32 - 2 sources")
+    if np.any(src < 0) or np.any(src >= np.array(shape)):
+        raise ValueError("a source lies outside the array")
+    d_mask = eng.to_device((lab != 0).astype(np.uint8))
+    lin = src[:, 0] + shape[0] * (src[:, 1] + shape[1] * src[:, 2])
+    d_dist, d_feat = feature.geodesic_voronoi(eng, d_mask, 1, shape, anisotropy, lin, np.arange(1, src.shape[0] + 1),
+                                              np.ones(src.shape[0]), features=return_feature_map)
+    host_shape = np.asarray(labels).shape
+    out = [d_dist.cpu().numpy().reshape(shape, order="F").reshape(host_shape, order="F")]
+    if return_max_location:
+        t = eng.torch
+        reach = t.where(t.isfinite(d_dist), d_dist, t.full_like(d_dist, -1.0))
+        loc = int(t.nonzero(reach == reach.max())[0].item())          # ties -> smallest linear index, like kh_edf_batch
+        out.append(tuple(int(v) for v in _pts([loc], shape)[0]))
+    if return_feature_map:
+        fm = d_feat.cpu().numpy().view(np.uint32)
+        fm[fm == _abi.NO_FEATURE] = 0
+        out.append(fm.reshape(shape, order="F").reshape(host_shape, order="F"))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 def euclidean_distance_field(labels, source, anisotropy=(1, 1, 1), free_space_radius=0, voxel_graph=None,
-                             return_max_location=False):
+                             return_max_location=False, return_feature_map=False):
     """dijkstra3d.euclidean_distance_field as called at kimimaro/trace.py:139-145, 302-307: geodesic distance inside
-    the mask from `source`, +inf elsewhere; with return_max_location also the (x, y, z) of the largest finite value."""
+    the mask from `source`, +inf elsewhere; with return_max_location also the (x, y, z) of the largest finite value.
+    `source` as an (n, 3) array of sources and / or return_feature_map=True (kimimaro/utility.py:613-617): the distance to the
+    nearest source and, with return_feature_map, which source that is -- (field[, max_location][, feature_map])."""
+    if return_feature_map or np.asarray(source).ndim == 2:
+        if voxel_graph is not None:
+            raise NotImplementedError("euclidean_distance_field from several sources does not take a voxel_graph (one-way edges)")
+        if free_space_radius:
+            raise NotImplementedError("euclidean_distance_field from several sources does not take a free_space_radius")
+        return _edf_many_sources(labels, source, anisotropy, return_max_location, return_feature_map)
     eng = engine()
     lab = _f3(labels)
     # voxel_graph: the directions a voxel's word does not allow leave the neighbour masks the search works from
