@@ -435,6 +435,34 @@ int kh_feature_relax(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz
 int kh_first_appearance(const uint32_t* feature, int64_t nvox, int64_t nnumbers, uint32_t* first_of_number, void* stream);
 int kh_remap_u32(uint32_t* feature, const uint32_t* map, int64_t nnumbers, int64_t nvox, void* stream);
 
+/* ---- kimimaro.synapses_to_targets (kimimaro/intake.py:706-745): the voxel of a label nearest to a centroid, for all labels and
+ * centroids in two passes over the volume (csrc/points.hip).
+ * labels: u8/u16/u32/u64 [sx,sy,sz] (label_bytes 1, 2, 4 or 8).  table: u64 [nlabels], the distinct labels asked for as the unsigned
+ * words the volume holds, ascending; query_start: u32 [nlabels + 1], the queries of table[k] are [query_start[k], query_start[k+1]);
+ * centroids: f64 [nqueries, 3] in voxel coordinates.  Both outputs are u64 [nqueries], set by the call:
+ *   best_distance[q] = bits of  d = sqrt(((x-cx)^2 + (y-cy)^2) + (z-cz)^2)  in float64, every operation rounded (what scipy's cdist
+ *                      computes), minimised over the voxels of the query's label;
+ *   best_voxel[q]    = x*sy*sz + y*sz + z (the C-order index: np.nonzero enumerates in C order whatever the memory layout) of the
+ *                      first such voxel in that order -- np.argmin's choice among equal distances.
+ * Both are ~0 ("none") for a query whose label does not occur.  Centroids must be finite.                                       */
+int kh_nearest_label_voxels(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz,
+                            const uint64_t* table, const uint32_t* query_start, int64_t nlabels, const double* centroids,
+                            int64_t nqueries, uint64_t* best_distance, uint64_t* best_voxel, void* stream);
+
+/* ---- skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086 -> skeletontricks.hpp:399-495) on the words of
+ * kh_neighbor_mask of the image (foreground = one label): every unordered pair of foreground voxels that are neighbours in one of
+ * `directions` (bit i = direction i of that mask: 0x3F connectivity 6, 0x3FFFF 18, 0x3FFFFFF 26) is an edge, every voxel on an edge a
+ * vertex.  The reference's numbering is the iteration order of an unordered_set; here it is canonical: vertices by
+ * ascending index x + sx*(y + sy*z), edges (a, b) with a < b sorted by a, then b.
+ * kh_binary_edge_count: is_vertex / n_owned (u8 [nvox]) = whether the voxel is a vertex / how many edges lead from it to LATER
+ *   voxels; totals (device u64 [2], set by the call) = number of vertices, number of edges.
+ * kh_binary_edge_emit: vertex_scan / edge_scan (i64 [nvox]) = the caller's INCLUSIVE prefix sums of is_vertex / n_owned;
+ *   vertices u32 [totals[0], 3] = (x, y, z) rows, edges u32 [totals[1], 2].  Fewer than 2^32 vertices.                           */
+int kh_binary_edge_count(const uint32_t* nbrmask, int64_t nvox, uint32_t directions, uint8_t* is_vertex, uint8_t* n_owned,
+                         uint64_t* totals, void* stream);
+int kh_binary_edge_emit(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz, uint32_t directions,
+                        const int64_t* vertex_scan, const int64_t* edge_scan, uint32_t* vertices, uint32_t* edges, void* stream);
+
 /* ---- kh_ccl26 on HOST memory (used for the 2-D faces of fix_borders and as a cross-check),
  * restating cc3d.connected_components as called at kimimaro/utility.py:74-77.
  * Returns the number of components (ids 1..N by first appearance in F-order raster).   */

@@ -10,10 +10,10 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 from ._abi import HipUnavailableError, KimiHipError  # noqa: F401
-from .intake import DEFAULT_TEASAR_PARAMS, DimensionError, skeletonize  # noqa: F401
+from .intake import DEFAULT_TEASAR_PARAMS, DimensionError, connect_points, skeletonize, synapses_to_targets  # noqa: F401
 from .lanes import skeletonize_many  # noqa: F401
 from .post import join_close_components, postprocess  # noqa: F401
 from .skeleton import Skeleton  # noqa: F401
-from .utility import oversegment  # noqa: F401
+from .utility import extract_skeleton_from_binary_image, oversegment  # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,0 +1,249 @@
+// points.hip -- the two point queries of the public interface that are whole-volume passes (gfx950).
+//
+//   kh_nearest_label_voxels   kimimaro.synapses_to_targets (kimimaro/intake.py:706-745): for every (label, centroid) query the voxel
+//                             of that label nearest to the centroid -- scipy's cdist + np.argmin(axis=0) over
+//                             np.vstack((labels == label).nonzero()).T, for ALL labels and centroids in two passes over the volume
+//                             instead of one pass and one dense distance matrix per label.
+//   kh_binary_edge_count /    skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086, skeletontricks.hpp:399-495)
+//   kh_binary_edge_emit       on the words of kh_neighbor_mask: count, (the caller's scan), emit -- in a canonical order instead of
+//                             the iteration order of an unordered_set.
+//
+// Both are HBM-bound sweeps with lanes along x.  Every global atomic on gfx950 is a fabric round trip: the nearest
+// voxel passes reduce inside the wave and ask the memory only when a lane beats what is already there; the edge count adds once
+// per wave.
+#include "common.h"
+
+namespace kh {
+
+static inline unsigned points_grid(int64_t n, int64_t cap) {
+  if (n > cap) n = cap;
+  if (n < 1) n = 1;
+  return (unsigned)n;
+}
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long o = __shfl_xor(v, d);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+__global__ void fill_u64_kernel(unsigned long long* p, int64_t n, unsigned long long v) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+// PASS 1: best_d[q] = min over the label's voxels of the bits of d (non-negative doubles order like u64).
+// PASS 2: best_c[q] = min C-order index x*sy*sz + y*sz + z over the label's voxels whose d has exactly those bits.
+// A block walks a CONTIGUOUS range of x tiles (256 voxels of one row): a thread's next voxel is the one 256 further along the row or
+// the same x of the next row, which mostly carries the label it has just looked up -- the search of the table is then skipped.
+template <typename LT, int PASS>
+__global__ __launch_bounds__(256) void nearest_kernel(const LT* __restrict__ lab, int sx, int sy, int sz, int64_t tiles_per_block,
+                                                      const unsigned long long* __restrict__ table, const uint32_t* __restrict__ qstart,
+                                                      int nlab, const double* __restrict__ cen, unsigned long long* best_d,
+                                                      unsigned long long* best_c) {
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * sy * sz;
+  const int64_t t0 = (int64_t)blockIdx.x * tiles_per_block;
+  const int64_t t1 = (t0 + tiles_per_block < ntiles) ? t0 + tiles_per_block : ntiles;
+  unsigned long long lastL = 0;
+  int lastSlot = -2;                      // -2: nothing looked up yet; -1: lastL is not in the table
+  for (int64_t t = t0; t < t1; t++) {
+    const int x = (int)(t % xt) * 256 + (int)threadIdx.x;
+    const int64_t r = t / xt;
+    const int y = (int)(r % sy), z = (int)(r / sy);
+    int slot = -1;
+    if (x < sx) {
+      const unsigned long long L = (unsigned long long)lab[x + (int64_t)sx * (y + (int64_t)sy * z)];
+      if (lastSlot == -2 || L != lastL) {
+        int lo = 0, hi = nlab;            // first entry >= L
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (table[mid] < L) lo = mid + 1; else hi = mid;
+        }
+        lastL = L;
+        lastSlot = (lo < nlab && table[lo] == L) ? lo : -1;
+      }
+      slot = lastSlot;
+    }
+    // the distinct labels of the wave, one after the other; the lanes of one label combine before anything goes to memory
+    unsigned long long todo = __ballot(slot >= 0);
+    while (todo) {
+      const int s = __shfl(slot, __ffsll((long long)todo) - 1);
+      const bool mine = slot == s;
+      todo &= ~__ballot(mine);
+      const uint32_t q0 = qstart[s], q1 = qstart[s + 1];
+      for (uint32_t q = q0; q < q1; q++) {
+        // scipy's euclidean kernel: s = 0; s += d*d per axis; sqrt(s) -- every operation rounded (no contraction in this library)
+        const double dx = (double)x - cen[3 * (size_t)q + 0];
+        const double dy = (double)y - cen[3 * (size_t)q + 1];
+        const double dz = (double)z - cen[3 * (size_t)q + 2];
+        const double d = __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+        const unsigned long long key = (unsigned long long)__double_as_longlong(d);
+        const unsigned long long cur = best_d[q];     // PASS 1: may be stale, i.e. too large -- costs an atomic, never a result
+        if (PASS == 1) {
+          if (!__any(mine && key < cur)) continue;
+          const unsigned long long m = wave_min_u64(mine ? key : ~0ull);
+          const unsigned long long holders = __ballot(mine && key == m);
+          if ((int)(threadIdx.x & 63) == __ffsll((long long)holders) - 1) atomicMin(&best_d[q], m);
+        } else {
+          const bool hit = mine && key == cur;
+          if (!__any(hit)) continue;
+          const unsigned long long c = ((unsigned long long)x * (unsigned long long)sy + (unsigned long long)y) * (unsigned long long)sz + (unsigned long long)z;
+          const unsigned long long m = wave_min_u64(hit ? c : ~0ull);
+          if (hit && c == m && m < best_c[q]) atomicMin(&best_c[q], m);
+        }
+      }
+    }
+  }
+}
+
+// the 13 directions of dir_delta whose neighbour comes LATER in the Fortran raster, as a mask
+__host__ __device__ constexpr uint32_t later_dirs() {
+  uint32_t m = 0;
+  for (int k = 0; k < 26; k++) {
+    int dx = 0, dy = 0, dz = 0;
+    dir_delta(k, dx, dy, dz);
+    if (dz > 0 || (dz == 0 && (dy > 0 || (dy == 0 && dx > 0)))) m |= 1u << k;
+  }
+  return m;
+}
+
+// per voxel: does it lie on an edge (a neighbour in one of the `dirs` directions), and how many edges does it own -- those to its
+// later neighbours.  totals[0] += vertices, totals[1] += edges: one atomic each per wave.
+__global__ __launch_bounds__(256) void binary_edge_count_kernel(const uint32_t* __restrict__ nbr, int64_t nvox, uint32_t dirs,
+                                                                uint8_t* __restrict__ is_vertex, uint8_t* __restrict__ n_owned,
+                                                                unsigned long long* totals) {
+  constexpr uint32_t LATER = later_dirs();
+  unsigned long long nv = 0, ne = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t m = nbr[i] & dirs;
+    const uint32_t own = (uint32_t)__popc(m & LATER);
+    is_vertex[i] = m != 0;
+    n_owned[i] = (uint8_t)own;
+    nv += m != 0;
+    ne += own;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    nv += __shfl_xor(nv, d);
+    ne += __shfl_xor(ne, d);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (nv) atomicAdd(&totals[0], nv);
+    if (ne) atomicAdd(&totals[1], ne);
+  }
+}
+
+// vscan / escan: INCLUSIVE scans of is_vertex / n_owned over the raster.  The lower-indexed voxel of a pair owns the edge and emits
+// its later neighbours in ascending index: rows (a, b), a < b, sorted by a, then b.
+__global__ __launch_bounds__(256) void binary_edge_emit_kernel(const uint32_t* __restrict__ nbr, int sx, int sy, int sz, uint32_t dirs,
+                                                               const int64_t* __restrict__ vscan, const int64_t* __restrict__ escan,
+                                                               uint32_t* __restrict__ vertices, uint32_t* __restrict__ edges) {
+  constexpr uint32_t LATER = later_dirs();
+  // the 13 later directions in ascending (dz, dy, dx), i.e. ascending linear index of the neighbour
+  constexpr int ORDER[13] = {1, 7, 3, 9, 21, 11, 23, 15, 5, 17, 24, 13, 25};
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * sy * sz;
+  const int64_t sxy = (int64_t)sx * sy;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int x = (int)(t % xt) * 256 + (int)threadIdx.x;
+    const int64_t r = t / xt;
+    const int y = (int)(r % sy), z = (int)(r / sy);
+    if (x >= sx) continue;
+    const int64_t i = x + (int64_t)sx * y + sxy * z;
+    const uint32_t m = nbr[i] & dirs;
+    if (m == 0) continue;
+    const int64_t rank = vscan[i] - 1;
+    vertices[3 * rank + 0] = (uint32_t)x;
+    vertices[3 * rank + 1] = (uint32_t)y;
+    vertices[3 * rank + 2] = (uint32_t)z;
+    const uint32_t own = m & LATER;
+    int64_t e = escan[i] - __popc(own);
+#pragma unroll
+    for (int j = 0; j < 13; j++) {
+      const int k = ORDER[j];
+      if (!((own >> k) & 1u)) continue;
+      int dx = 0, dy = 0, dz = 0;
+      dir_delta(k, dx, dy, dz);
+      // (a set bit says the neighbour is inside the volume and foreground: its mask has the opposite bit, so it is a vertex)
+      edges[2 * e + 0] = (uint32_t)rank;
+      edges[2 * e + 1] = (uint32_t)(vscan[i + dx + (int64_t)sx * dy + sxy * dz] - 1);
+      e++;
+    }
+  }
+}
+
+}  // namespace kh
+
+using namespace kh;
+
+#define KH_POINTS_DISPATCH(bytes, CALL)                      \
+  switch (bytes) {                                           \
+    case 1: { typedef uint8_t LT; CALL; } break;             \
+    case 2: { typedef uint16_t LT; CALL; } break;            \
+    case 4: { typedef uint32_t LT; CALL; } break;            \
+    case 8: { typedef uint64_t LT; CALL; } break;            \
+    default: set_error("label_bytes must be 1, 2, 4 or 8"); return KH_EINVAL; \
+  }
+
+extern "C" int kh_nearest_label_voxels(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz,
+                                       const uint64_t* table, const uint32_t* query_start, int64_t nlabels, const double* centroids,
+                                       int64_t nqueries, uint64_t* best_distance, uint64_t* best_voxel, void* stream) {
+  if (int rc = require_device()) return rc;
+  if (sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) || sy >= (1ll << 31) || sz >= (1ll << 31) || nlabels <= 0 ||
+      nlabels >= (1ll << 31) || nqueries <= 0 || nqueries >= (1ll << 32)) {
+    set_error("kh_nearest_label_voxels: extents in [1, 2^31), 1 <= nlabels < 2^31, 1 <= nqueries < 2^32");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(fill_u64_kernel, dim3(points_grid((nqueries + 255) / 256, 1024)), dim3(256), 0, st,
+                     (unsigned long long*)best_distance, nqueries, ~0ull);
+  hipLaunchKernelGGL(fill_u64_kernel, dim3(points_grid((nqueries + 255) / 256, 1024)), dim3(256), 0, st,
+                     (unsigned long long*)best_voxel, nqueries, ~0ull);
+  const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
+  const unsigned grid = points_grid(ntiles, 4096);
+  const int64_t per_block = (ntiles + grid - 1) / grid;
+  KH_POINTS_DISPATCH(label_bytes, hipLaunchKernelGGL((nearest_kernel<LT, 1>), dim3(grid), dim3(256), 0, st, (const LT*)labels, (int)sx,
+                                                     (int)sy, (int)sz, per_block, (const unsigned long long*)table, query_start,
+                                                     (int)nlabels, centroids, (unsigned long long*)best_distance,
+                                                     (unsigned long long*)best_voxel));
+  KH_POINTS_DISPATCH(label_bytes, hipLaunchKernelGGL((nearest_kernel<LT, 2>), dim3(grid), dim3(256), 0, st, (const LT*)labels, (int)sx,
+                                                     (int)sy, (int)sz, per_block, (const unsigned long long*)table, query_start,
+                                                     (int)nlabels, centroids, (unsigned long long*)best_distance,
+                                                     (unsigned long long*)best_voxel));
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_binary_edge_count(const uint32_t* nbrmask, int64_t nvox, uint32_t directions, uint8_t* is_vertex, uint8_t* n_owned,
+                                    uint64_t* totals, void* stream) {
+  if (int rc = require_device()) return rc;
+  if (nvox <= 0) {
+    set_error("kh_binary_edge_count: nvox must be positive");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(fill_u64_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)totals, (int64_t)2, 0ull);
+  hipLaunchKernelGGL(binary_edge_count_kernel, dim3(points_grid((nvox + 255) / 256, 4096)), dim3(256), 0, st, nbrmask, nvox,
+                     directions, is_vertex, n_owned, (unsigned long long*)totals);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_binary_edge_emit(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz, uint32_t directions,
+                                   const int64_t* vertex_scan, const int64_t* edge_scan, uint32_t* vertices, uint32_t* edges,
+                                   void* stream) {
+  if (int rc = require_device()) return rc;
+  if (sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) || sy >= (1ll << 31) || sz >= (1ll << 31)) {
+    set_error("kh_binary_edge_emit: extents in [1, 2^31)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
+  hipLaunchKernelGGL(binary_edge_emit_kernel, dim3(points_grid(ntiles, 1 << 20)), dim3(256), 0, st, nbrmask, (int)sx, (int)sy, (int)sz,
+                     directions, vertex_scan, edge_scan, vertices, edges);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}

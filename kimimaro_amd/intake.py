@@ -201,6 +201,119 @@ def skeletonize(all_labels, teasar_params=DEFAULT_TEASAR_PARAMS, anisotropy=(1, 
                           timings=_timings, d_dbf=avocado, d_graph=d_graph)
 
 
+def _label_word(label, span, itemsize):
+    """the unsigned word a volume whose dtype holds `span` = (smallest, largest) stores for `label`, None when `labels == label`
+    is False everywhere whatever the volume holds (a value outside the dtype, a fraction, something that is no number)"""
+    try:
+        value = int(label)
+        if value != label:
+            return None
+    except (TypeError, ValueError, OverflowError):
+        return None
+    if not span[0] <= value <= span[1]:
+        return None
+    return value % (1 << (8 * itemsize))
+
+
+def synapses_to_targets(labels, synapses, progress=False):
+    """kimimaro.synapses_to_targets (kimimaro/intake.py:706-745): turn the output of synapse detection into targets for
+    skeletonize(extra_targets_after=...).  synapses: { label: [ (centroid, swc_label), ... ] }, centroid an (x, y, z) float triple in
+    voxel coordinates.  For every label that occurs in the volume and every swc label of its pairs, the voxels of the label nearest
+    to the centroids become targets.  Returns { (x, y, z): swc_label } with tuples of ints.
+
+    The reference compares the volume with one label at a time and builds a dense cdist matrix per label; here all labels and all
+    centroids go to the MI355X in one call (kh_nearest_label_voxels, two passes over the volume).  Distances are scipy's float64
+    ones, among equally near voxels the first in C order wins (np.argmin over np.nonzero's enumeration).  Insertion and overwrite
+    order are the reference's: labels in the order of `synapses`; within a label the swc labels in first-seen order; within an swc
+    label the distinct winners in ascending C order; a later entry overwrites an equal key's value and keeps its place.
+    labels: numpy, or a torch tensor on the GPU indexed [x, y, z].  Trailing axes beyond the third are dropped (`labels[..., 0]`,
+    as the reference does); what is not 3-D then is a DimensionError.  `progress` is accepted and has no effect."""
+    if len(synapses) == 0:
+        return {}
+    while labels.ndim > 3:
+        labels = labels[..., 0]
+    if labels.ndim != 3:
+        raise DimensionError("synapses_to_targets needs a 3-D label volume. Got: {}".format(tuple(labels.shape)))
+    from . import points
+    from .ops import engine
+    from .utility import _device_labels
+    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    d_flat, itemsize, _, shape, _, span = _device_labels(eng, labels)
+    sx, sy, sz = shape
+
+    # per label that the dtype can hold: its swc labels in first-seen order, each with its centroids (intake.py:735-737)
+    groups, by_word = [], {}
+    for label, pairs in synapses.items():
+        word = _label_word(label, span, itemsize)
+        swc = {}
+        for centroid, swc_label in pairs:
+            swc.setdefault(swc_label, []).append(np.asarray(centroid, dtype=np.float64).reshape(3))
+        if word is None or not swc or word in by_word:
+            groups.append(None)
+            continue
+        by_word[word] = len(groups)
+        groups.append((word, swc))
+    if not by_word:
+        return {}
+    words = np.array(sorted(by_word), dtype=np.uint64)
+    counts = [sum(len(c) for c in groups[by_word[int(w)]][1].values()) for w in words]
+    query_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint32)
+    centroids = np.concatenate([np.stack(c) for w in words for c in groups[by_word[int(w)]][1].values()])
+    winners = points.nearest_label_voxels(eng, d_flat, itemsize, shape, words, query_start, centroids)
+
+    targets = {}
+    for g in groups:
+        if g is None:
+            continue
+        word, swc = g
+        at = int(query_start[int(np.searchsorted(words, np.uint64(word)))])
+        for swc_label, cens in swc.items():
+            won = winners[at:at + len(cens)]
+            at += len(cens)
+            if won[0] == points.NONE64:              # the label does not occur (intake.py:732-733)
+                break
+            for c in np.unique(won).tolist():        # np.unique(np.argmin(...)): ascending C order
+                targets[(c // (sy * sz), (c // sz) % sy, c % sz)] = swc_label
+    return targets
+
+
+def connect_points(labels, start, end, anisotropy=(1, 1, 1), fill_holes=False, in_place=False, pdrf_scale=100000, pdrf_exponent=4):
+    """kimimaro.connect_points (kimimaro/intake.py:268-313): one centerline between two chosen voxels of a 2-D or 3-D binary image,
+    in physical units.  The connected components come from the GPU CCL (kh_ccl26), the path from kimimaro_amd.trace.point_to_point.
+    start / end: (x, y, z), or (x, y) for a 2-D image.  ValueError when `start` is background or the two lie in different
+    components.  labels: numpy, or a torch tensor indexed [x, y, z].  `fill_holes` is accepted and ignored, as the reference ignores it."""
+    anisotropy = np.array(anisotropy, dtype=np.float32)
+    start, end = tuple(start), tuple(end)
+    if hasattr(labels, "permute") and hasattr(labels, "cpu"):          # a torch tensor: the searches below take host arrays
+        labels = labels.cpu().numpy()
+    planar = np.ndim(labels) == 2
+    labels = format_labels(np.asarray(labels).astype(bool), in_place=in_place)
+    pts = []
+    for pt in (start, end):
+        pt = tuple(int(v) for v in pt)
+        if planar and len(pt) == 2:
+            pt += (0,)
+        if len(pt) != 3 or any(not 0 <= v < s for v, s in zip(pt, labels.shape)):
+            raise IndexError("point {} is outside an image of shape {}".format(pt, labels.shape))
+        pts.append(pt)
+    start, end = pts
+
+    from .ops import engine
+    from .trace import point_to_point
+    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    d_cc, _, _ = compute_cc_labels_device(eng, labels)
+    eng._narrow = None                               # (the u16 copy of the component ids is not kept alive past this call)
+    cc = LazyVolume(eng, d_cc, labels.shape)
+    if cc[start] == 0 or cc[start] != cc[end]:
+        raise ValueError("Cannot extract centerline from disconnected components.")
+    del cc, d_cc
+
+    skel = point_to_point(labels, start, end, anisotropy=anisotropy, pdrf_scale=pdrf_scale, pdrf_exponent=pdrf_exponent)
+    skel.vertices *= anisotropy
+    skel.space = "physical"
+    return skel
+
+
 def _avocado_fruit_from_lines(xl, yl, zl, cx, cy, cz, background=0):
     """kimimaro.skeletontricks.find_avocado_fruit (skeletontricks.pyx:905-992) on the three axis-parallel lines of the label volume
     through (cx, cy, cz) (host copies): six rays from the voxel, each ends at the background or at the first other label, which it

@@ -347,6 +347,19 @@ def dijkstra(field, source, target, voxel_graph=None):
     return s.run(2, src, _loc(target, s.shape))     # parents array cannot express: DESIGN.md 3.3)
 
 
+def extract_edges_from_binary_image(binimg, connectivity=26):
+    """kimimaro.skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086): (vertices uint32 (n, 3), edges uint32
+    (m, 2)) of a 2-D / 3-D binary image, foreground = non-zero: the pairs of foreground voxels that are neighbours (6: along an
+    axis, 18: also across a face diagonal, 26: also across a corner) and the voxels that lie on such a pair.  The reference numbers
+    them in the iteration order of an unordered_set; here vertices come by ascending Fortran index, edges as (a, b), a < b, sorted
+    by a, then b.  binimg: numpy, or a torch tensor on the GPU; bool or any integer dtype."""
+    from . import points
+    img = points.check_binary_image(binimg)          # TypeError / DimensionError before anything touches the GPU
+    eng = engine()
+    d_img, shape = points.device_binary_image(eng, img)
+    return points.binary_edges(eng, d_img, shape, connectivity)
+
+
 def first_label(labels):
     """kimimaro.skeletontricks.first_label (skeletontricks.pyx:307-326): (x, y, z) of the first non-zero voxel in the
     z / y / x raster, None when there is none."""

@@ -1,0 +1,109 @@
+"""Device plumbing of the two point queries (csrc/points.hip): the voxel of a label nearest to a centroid
+(kimimaro_amd.intake.synapses_to_targets) and the edges of a binary image (kimimaro_amd.ops.extract_edges_from_binary_image).
+Everything works on whole-volume arrays resident in HBM; the library allocates nothing, the scratch is sized here."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _abi
+
+NONE64 = 0xFFFFFFFFFFFFFFFF       # the "none" word of kh_nearest_label_voxels
+MAX_EDGES = 2 ** 31
+
+
+def connectivity_directions(connectivity):
+    """the directions of kh_neighbor_mask's words that skeletontricks.hpp:399-440 visits: the axis offsets always, the face
+    diagonals for `connectivity > 6`, the corners for `connectivity > 18` (its own comparisons)"""
+    connectivity = int(connectivity)
+    if connectivity > 18:
+        return 0x3FFFFFF
+    if connectivity > 6:
+        return 0x3FFFF
+    return 0x3F
+
+
+def nearest_label_voxels(eng, d_lab, label_bytes, shape, words, query_start, centroids):
+    """d_lab: the label volume on the device (1-D, Fortran order, label_bytes 1 / 2 / 4 / 8); words: the distinct labels asked for as
+    the unsigned words the volume holds, ascending (u64 host array); query_start: u32 [len(words) + 1]; centroids: f64 [Q, 3], the
+    queries of words[k] at rows [query_start[k], query_start[k + 1]).  One call for all of them.  Returns the u64 host array [Q] of
+    the winners' C-order indices x*sy*sz + y*sz + z, NONE64 for a label that does not occur."""
+    t, P = eng.torch, eng.ptr
+    sx, sy, sz = (int(v) for v in shape)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    query_start = np.ascontiguousarray(query_start, dtype=np.uint32)
+    centroids = np.ascontiguousarray(centroids, dtype=np.float64).reshape(-1, 3)
+    nq = int(centroids.shape[0])
+    assert words.size >= 1 and query_start.size == words.size + 1 and int(query_start[-1]) == nq and nq >= 1
+    assert np.all(words[1:] > words[:-1])
+    if not np.all(np.isfinite(centroids)):
+        raise ValueError("centroids must be finite")
+    d_words = t.from_numpy(words.view(np.int64)).to(eng.device)
+    d_start = t.from_numpy(query_start.view(np.int32)).to(eng.device)
+    d_cen = t.from_numpy(centroids).to(eng.device)
+    d_best = eng.empty(nq, t.int64)
+    d_vox = eng.empty(nq, t.int64)
+    _abi.check(eng.lib.kh_nearest_label_voxels(P(d_lab), label_bytes, sx, sy, sz, P(d_words), P(d_start), int(words.size), P(d_cen), nq,
+                                               P(d_best), P(d_vox), eng.stream()))
+    return d_vox.cpu().numpy().view(np.uint64)
+
+
+def binary_edges(eng, d_img, shape, connectivity=26):
+    """d_img: u8 device tensor [nvox] in Fortran order, foreground = 1 (0 / 1 only: the neighbour masks compare labels).
+    Returns (vertices u32 (n, 3), edges u32 (m, 2)) as host arrays in the canonical order: vertices by ascending Fortran index,
+    edges (a, b) with a < b sorted by a, then b.  A foreground voxel without a foreground neighbour is no vertex."""
+    t, P = eng.torch, eng.ptr
+    sx, sy, sz = (int(v) for v in shape)
+    nvox = sx * sy * sz
+    none = np.zeros((0, 3), dtype=np.uint32), np.zeros((0, 2), dtype=np.uint32)
+    if nvox == 0:
+        return none
+    dirs = connectivity_directions(connectivity)
+    d_nbr = eng.empty(nvox, t.int32)
+    _abi.check(eng.lib.kh_neighbor_mask(P(d_img), 1, sx, sy, sz, P(d_nbr), eng.stream()))
+    d_isv = eng.empty(nvox, t.uint8)
+    d_own = eng.empty(nvox, t.uint8)
+    d_tot = eng.empty(2, t.int64)
+    _abi.check(eng.lib.kh_binary_edge_count(P(d_nbr), nvox, dirs, P(d_isv), P(d_own), P(d_tot), eng.stream()))
+    nvert, nedge = (int(v) for v in d_tot.cpu().numpy())
+    if nedge > MAX_EDGES:
+        raise ValueError("the image has %d edges, more than 2^31: a skeleton image is sparse" % nedge)
+    if nedge == 0:
+        return none
+    d_vscan = t.cumsum(d_isv, 0, dtype=t.int64)
+    d_escan = t.cumsum(d_own, 0, dtype=t.int64)
+    del d_isv, d_own
+    d_vert = eng.empty(3 * nvert, t.int32)
+    d_edge = eng.empty(2 * nedge, t.int32)
+    _abi.check(eng.lib.kh_binary_edge_emit(P(d_nbr), sx, sy, sz, dirs, P(d_vscan), P(d_escan), P(d_vert), P(d_edge), eng.stream()))
+    return (d_vert.cpu().numpy().view(np.uint32).reshape(nvert, 3), d_edge.cpu().numpy().view(np.uint32).reshape(nedge, 2))
+
+
+def check_binary_image(image):
+    """The checks that need no GPU: the dtype (bool or integers) and the dimensions (a fourth non-trivial axis is a DimensionError).
+    numpy -> the u8 array of 0 / 1 with three axes, Fortran ordered; a torch tensor comes back with at most three axes."""
+    from .intake import DimensionError, format_labels
+    if hasattr(image, "permute") and hasattr(image, "device"):          # a torch tensor
+        if image.dtype.is_floating_point or image.dtype.is_complex:
+            raise TypeError("the image must be bool or integers")
+        extents = tuple(int(v) for v in image.shape)
+        if any(e != 1 for e in extents[3:]):
+            raise DimensionError("Input labels may be no more than three non-trivial dimensions. Got: {}".format(extents))
+        return image.reshape(extents[:3]) if len(extents) > 3 else image
+    arr = np.asarray(image)
+    if arr.dtype != np.bool_ and arr.dtype.kind not in "ui":
+        raise TypeError("the image must be bool or integers")
+    return format_labels(arr != 0, in_place=True)
+
+
+def device_binary_image(eng, image):
+    """what check_binary_image returned -> (u8 device tensor of 0 / 1 in Fortran order, (sx, sy, sz)); a tensor (indexed [x, y(, z)])
+    must live on the engine's device and gets trailing axes up to three"""
+    t = eng.torch
+    if isinstance(image, np.ndarray):
+        return eng.to_device(image), tuple(int(v) for v in image.shape)
+    if image.device != eng.device:
+        raise ValueError("an image tensor must live on the engine's device (%s)" % eng.device)
+    vol = image
+    while vol.ndim < 3:
+        vol = vol.unsqueeze(-1)
+    return (vol != 0).permute(2, 1, 0).contiguous().reshape(-1).to(t.uint8), tuple(int(v) for v in vol.shape)

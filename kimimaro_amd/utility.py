@@ -13,8 +13,19 @@ import numpy as np
 
 from . import _abi, feature
 from .intake import format_labels
+from .skeleton import Skeleton
 
 SEGMENTS_ATTRIBUTE = {"id": "segments", "data_type": "uint64", "num_components": 1}    # utility.py:583-587
+
+
+def extract_skeleton_from_binary_image(image):
+    """kimimaro.extract_skeleton_from_binary_image (kimimaro/utility.py:54-56): turn a binary image that another algorithm has
+    thinned already into a Skeleton -- every foreground voxel with a foreground 26-neighbour is a vertex, every such pair an edge
+    (kimimaro_amd.ops.extract_edges_from_binary_image: the canonical numbering of DESIGN.md 3.11).  image: numpy, or a torch tensor
+    on the GPU indexed [x, y(, z)]; bool or integers, foreground = non-zero."""
+    from .ops import extract_edges_from_binary_image
+    verts, edges = extract_edges_from_binary_image(image)
+    return Skeleton(verts, edges)
 
 
 def _skeleton_list(skeletons):
