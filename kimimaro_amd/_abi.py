@@ -54,6 +54,9 @@ SWEEP_LDS_LEVELS = 16384  # KH_SWEEP_LDS_LEVELS
 SWEEP_MAX_LEVELS = 1 << 22  # labels with more levels than this use the heap emulation only
 PDRF_BASE, PDRF_FINISH = -1, -2  # KH_PDRF_BASE / KH_PDRF_FINISH
 PDRF_KEEP_OTHERS = 0x100         # KH_PDRF_KEEP_OTHERS
+# flags of kh_trace_paths (KH_TRACE_*; tests/test_abi.py compares them with the header)
+TRACE_PROFILE, TRACE_HEAP_PRIO, TRACE_THREADS_64, TRACE_THREADS_128, TRACE_NO_GHOSTS, TRACE_GHOST_PARANOID = 1, 2, 4, 8, 16, 32
+TRACE_BIG_LDS_HEAP, TRACE_VOXEL_GRAPH, TRACE_SCRATCH_POOL, TRACE_FUSED_EDF = 64, 128, 256, 512
 BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of kh_geodesic_relax / kh_feature_relax
 NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
 

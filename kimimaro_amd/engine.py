@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -28,134 +29,10 @@ def _torch():
     return torch
 
 
-# per-label scratch of the path loop as plan_launches books it: work lists 16 B per voxel, heap 24, event arena ~24, voxel list and DAF
-# 8, ghost journal 8, path buffers and saved rail weights ~6 = 86 B, booked as 110; + the fixed parts of a small label (a 32 768-node
-# heap, the arena's level chunks, 64 Ki path slots).  Round 2 booked 300 B per voxel (28 GB of event arena per c3 volume then):
-# c5 ran as three launches one after the other, 12.4 s of paths; as one launch it is 91 -> ~200 GB of HBM and half the time.
-SCRATCH_BYTES_PER_VOXEL = 60        # round 6: voxel list + DAF 8, work lists 16, the pool's share of heap and journal ~5, path buffers ~1,
-SCRATCH_BYTES_PER_LABEL = 3 << 19    # booked with slack; per label: the event arena (1.25 x the level window + 320 chunks: 0.6-1.4 MB)
-# Round 6: heap and ghost journal come out of one pool per launch, on demand (KH_TRACE_SCRATCH_POOL): this fraction of what all
-# labels together could ask for (c3: 141 of 3 402 labels ever run the heap emulation -- 6 % of the nodes --, 360 ever hold a ghost);
-# a label the pool cannot serve is traced again with scratch of its own, like every other overflow
-SCRATCH_POOL_FRACTION = float(os.environ.get("KH_SCRATCH_POOL_FRACTION", "0.15"))
-
-
-def plan_launches(counts, budget):
-    """Groups of label positions for successive launches of the path loop: largest labels first, a group is closed when the
-    next label's scratch (SCRATCH_BYTES_PER_VOXEL per voxel + SCRATCH_BYTES_PER_LABEL) would take it over `budget` bytes; a label
-    larger than the budget gets a launch of its own.  One group = everything fits."""
-    counts = np.asarray(counts, dtype=np.int64)
-    need = counts * SCRATCH_BYTES_PER_VOXEL + SCRATCH_BYTES_PER_LABEL
-    if int(need.sum()) <= budget:
-        return [list(range(len(counts)))]
-    groups, cur, acc = [], [], 0
-    for i in np.argsort(-counts, kind="stable").tolist():
-        if cur and acc + int(need[i]) > budget:
-            groups.append(cur)
-            cur, acc = [], 0
-        cur.append(i)
-        acc += int(need[i])
-    groups.append(cur)
-    return groups
-
-
-SCHED_LEVELS = (1 << 17) - 1     # SW_SCHED_LEVELS (csrc/sweep.h): labels with more levels run the sweep unfiltered
-
-
-def plan_arena(cnt, nlev, filtered, window=None):
-    """(log2 slots per chunk, chunks) of the sweep's event arena per label (numpy arrays; csrc/sweep.h: fixed-size chunks of
-    8-byte events chained per level; the chunks of a level go back to a free stack when the level has been processed).
-    Unfiltered a voxel is handed ~13 events per call; with the pending-deadline filter ~2 (measured at c3: 1.72e9 -> 2.8e8
-    events per volume), and a level of a large call holds tens of events instead of hundreds -- smaller chunks, a fraction of
-    the event budget.  What has to fit is what is PENDING at one time: one partly filled chunk per level that has events
-    (at most `window` levels when the label has a level window, never more levels than the label can get events) plus the
-    pending events themselves.  An arena that runs out makes the call fall back to the heap emulation (SW_BAIL_ARENA in
-    stat_sweep_why): a matter of speed, not of results."""
-    cnt = np.asarray(cnt, dtype=np.int64)
-    nlev = np.asarray(nlev, dtype=np.int64)
-    filt = np.asarray(filtered, dtype=bool) & (nlev <= SCHED_LEVELS)
-    shift = np.where(filt, np.where(cnt >= 65536, 6, 5), np.where(cnt >= 32768, 7, 6)).astype(np.int64)
-    per_voxel = np.where(filt, 3, 14)
-    levels = np.where(filt, np.minimum(nlev, 3 * cnt + 64), nlev)
-    if window is not None:
-        window = np.asarray(window, dtype=np.int64)
-        levels = np.where(window > 0, np.minimum(levels, window), levels)
-    chunks = levels + levels // 2 + ((per_voxel * cnt) >> shift) + 320
-    if window is not None:
-        # Round 6, measured on c3 (`cyc_push` of the task records = most chunks a label ever had in use): 0.41 x the window on average,
-        # 0.94 x at the 99th percentile, 1.21 x at most -- the chunks of a level go back to the label's free stack when the level is
-        # done, so what is in use is what is PENDING, and that is bounded by the window, not by the label's size.  The arena was
-        # 6.9 GB per c3 volume for 0.55 GB of use, and the volumes in flight are bounded by memory.
-        chunks = np.where(window > 0, np.minimum(chunks, window + window // 4 + 320), chunks)
-    chunks = np.minimum(chunks, (1 << 20) - 2)    # 20-bit chunk ids (SW_NOCHUNK)
-    return shift, chunks
-
-
-def plan_spill(cnt):
-    """entries (a power of two) of the sweep's candidate-spill table per label (csrc/sweep.h: the fifth to eighth possible
-    owner of a voxel; 12 bytes per entry at the front of the label's arena).  Few voxels ever need one -- five in the label
-    of c3 whose longest call used to be abandoned for them -- so the table is small: Nf / 64, between 256 and 16384 entries."""
-    cnt = np.maximum(np.asarray(cnt, dtype=np.int64), 1)
-    return 2 ** np.clip(np.ceil(np.log2(cnt / 64.0)), 8, 14).astype(np.int64)
-
-
-def arena_units(chunks, shift, spill):
-    """256-byte units of a label's arena: [spill table: 12 B per entry][free stack: 4 B per chunk][chunks of 8-byte slots]"""
-    return (spill * 12 + 255) // 256 + (chunks * 4 + 255) // 256 + ((chunks * 8) << shift) // 256
-
-
-def level_windows(keys, anisotropy, nlev, lds_levels):
-    """kh_label_t.lev_window per label (numpy u32): a power of two above the number of levels an event can lie ahead of the
-    level being processed, or 0 when that does not fit `lds_levels` words.  An event's key is the distance of a 26-neighbour
-    of the processed voxel from a source whose key of that voxel is not above the current one, so it exceeds the current key
-    by one step (the longest neighbour offset) at most: the bound is the largest number of distinct keys in such an interval
-    over the label's levels, taken from the sorted key table itself (+ slack for the keys' own rounding)."""
-    keys = np.asarray(keys, dtype=np.float64)
-    nlev = np.asarray(nlev, dtype=np.int64)
-    if keys.size == 0:
-        return np.zeros(nlev.shape, dtype=np.uint32)
-    step = float(np.sqrt(sum(float(np.float32(a)) ** 2 for a in anisotropy)))
-    ahead = np.searchsorted(keys, (keys + step) * (1.0 + 1e-6) + 1e-6, side="right") - 1 - np.arange(keys.size)
-    worst = np.maximum.accumulate(ahead)                         # worst[i] = most levels ahead over levels 0..i
-    w = worst[np.clip(nlev - 1, 0, keys.size - 1)] + 2
-    win = np.maximum(64, 2 ** np.ceil(np.log2(np.maximum(w, 1))).astype(np.int64))
-    return np.where((nlev > 0) & (win <= int(lds_levels)), win, 0).astype(np.uint32)
-
-
-def int_key_mode(anisotropy, rmax):
-    """(gq, gx, gy, gz) of the sweep's INTEGER levels (csrc/sweep.h) for balls up to `rmax`, or None when the table of ranks
-    has to serve.  With an integral anisotropy the flood's key of an offset (a, b, c) is sqrtf of the exact integer
-    T = (wx a)^2 + (wy b)^2 + (wz c)^2 as long as T < 2^24 (every product and partial sum is an integer below 2^24: no rounding
-    before the square root), and T = gq * S with gq = gcd(wx^2, wy^2, wz^2), S = gx a^2 + gy b^2 + gz c^2.  sqrtf is monotone; two
-    values of T that differ lie at least gq apart, i.e. their roots gq / (2 sqrt T) apart, which exceeds an ulp of sqrt T
-    (<= sqrt T * 2^-23) while T < gq * 2^22 -- taken with a factor two of margin.  Then S orders the keys and tells equal ones exactly as
-    the floats do, for every offset the sweep evaluates: the voxels of a ball and their neighbours (one step further out)."""
-    w = [float(np.float32(a)) for a in anisotropy]
-    if any(v < 1.0 or v != int(v) or v > 4096.0 for v in w) or not np.isfinite(rmax) or rmax <= 0:
-        return None
-    q = [int(v) * int(v) for v in w]
-    gq = int(np.gcd.reduce(q))
-    step = float(np.sqrt(sum(q)))
-    tmax = (float(rmax) + step) ** 2 * (1.0 + 1e-6)
-    if tmax >= 2.0 ** 24 or tmax >= gq * 2.0 ** 21:
-        return None
-    return gq, q[0] // gq, q[1] // gq, q[2] // gq
-
-
-def int_levels(anisotropy, gq, rmax, lds_levels):
-    """per label (numpy arrays over `rmax`): the number of integer levels a ball of that radius can touch and the level window
-    (a power of two above the number of levels an event can lie ahead of the level being processed, 0 when that does not fit
-    `lds_levels` words).  An event's level is S of a 26-neighbour of the processed voxel from a source whose key of that voxel is
-    not above the current one: at most ((d + step)^2 - d^2) / gq levels ahead for d up to the radius."""
-    rmax = np.asarray(rmax, dtype=np.float64)
-    w = [float(np.float32(a)) for a in anisotropy]
-    step = float(np.sqrt(sum(v * v for v in w)))
-    ok = np.isfinite(rmax) & (rmax > 0)
-    r = np.where(ok, rmax, 0.0)
-    nlev = np.where(ok, np.floor(r * r * (1.0 + 1e-6) / gq) + 2, 0).astype(np.int64)
-    ahead = np.ceil((2.0 * r * step + step * step) * (1.0 + 1e-6) / gq) + 2
-    win = np.maximum(64, 2 ** np.ceil(np.log2(np.maximum(ahead, 1))).astype(np.int64))
-    return nlev, np.where(ok & (win <= int(lds_levels)), win, 0).astype(np.int64)
+# the launch plan is pure numpy and lives in kimimaro_amd.plan; its names stay importable from here
+from .plan import (SCHED_LEVELS, SCRATCH_BYTES_PER_LABEL, SCRATCH_BYTES_PER_VOXEL, SCRATCH_POOL_FRACTION, SWEEP_FIELDS,  # noqa: F401
+                   LabelSet, arena_units, int_key_mode, int_levels, label_order, level_windows, plan_arena, plan_launches,
+                   plan_spill, plan_sweep, plan_tasks, sweep_radii)
 
 
 class Engine:
@@ -175,7 +52,6 @@ class Engine:
         self.split_slots = int(os.environ.get("KH_SPLIT_SLOTS", "256"))   # labels that go to the second stream (one big-LDS workgroup per CU) when results are consumed incrementally
         self.split_min_voxels = 16384       # ... if they have at least this many voxels
         self.sweep = os.environ.get("KH_SWEEP", "1") != "0"   # False: every invalidation runs as the heap emulation (tests, comparisons)
-        self.sweep_filter = True            # (the pending-deadline filter of the sweep is no longer optional: its words also say "dead")
         # integer levels (csrc/sweep.h) whenever the anisotropy allows them; False: always the table of ranks (tests, A/B runs)
         self.int_keys = os.environ.get("KH_SWEEP_INT_KEYS", "1") != "0"
         # heap and ghost journal of a launch's labels from one pool, on demand (False: a slice per label, rounds 1-5)
@@ -534,23 +410,14 @@ class Engine:
         ctx["d_gate"] = d_gate
         ctx.update(d_slot=d_slot, d_lists=d_lists, d_nbr=d_nbr, d_queues=self.empty(4 * (cnt + 64), t.int32),
                    d_heap=self.empty(2 * hcap, t.int64), d_qstate=t.zeros(nvox + 4, dtype=t.uint8, device=self.device))
-        d_rank, rdims, max_nlev, ev_units = None, (0, 0, 0), 0, 0
         rmax = float(np.float32(rmax))
-        sweep_on = False
-        if self.sweep and cnt > 0 and np.isfinite(rmax) and rmax > 0:
-            lv = self.sweep_levels(shape, anisotropy, [rmax], [cnt])
-            if lv is not None and int(lv["nlev"][0]) > 0:
-                nlev, win = int(lv["nlev"][0]), int(lv["win"][0])
-                shift, chunks = (int(v) for v in plan_arena(cnt, nlev, True, win))
-                in_lds = win > 0 or nlev <= self.sweep_lds_levels       # else: heap emulation only (the kernel decides the same)
-                spill = int(plan_spill(cnt))
-                ev_units = int(arena_units(chunks, shift, spill))   # spill table, (unused stack), chunks
-                task["nlev"], task["sweep_rmax"], task["ev_chunks"], task["ev_shift"] = nlev, np.float32(rmax), chunks, shift
-                task["ev_spill"] = spill
-                task["lev_window"] = win
-                max_nlev = win if win > 0 else (nlev if in_lds else 0)
-                d_rank, rdims = lv["d_rank"], lv["rdims"]
-                sweep_on = True
+        lv = self.sweep_levels(shape, anisotropy, [rmax], [cnt]) if self.sweep and cnt > 0 and np.isfinite(rmax) and rmax > 0 else None
+        # (no window cap, no arena divisor; keep_unfit: this record books arena and spill table whatever the levels fit)
+        sw = plan_sweep([cnt], np.array([rmax], dtype=np.float32), lv, lds_levels=self.sweep_lds_levels, keep_unfit=True)
+        for key in SWEEP_FIELDS:
+            task[key] = getattr(sw, key)
+        sweep_on, max_nlev, ev_units = sw.sweep_on, sw.max_nlev, sw.ev_total
+        d_rank, rdims = (lv["d_rank"], lv["rdims"]) if sweep_on else (None, (0, 0, 0))
         d_arena = self.empty(max(ev_units, 1) * 32 + 32, t.int64)
         ctx.update(d_rank=d_rank, rdims=rdims, max_nlev=max_nlev, d_arena=d_arena,
                    arena_ptr=C.c_void_p((d_arena.data_ptr() + 255) & ~255),
@@ -582,457 +449,368 @@ class Engine:
         return int(d_cnt.item()), task
 
     # -- the per-label pipeline -------------------------------------------------
-    def run_labels(self, d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels, segids, counts, dbf_max, first_index,
-                   xmin, xmax, roots, targets_before, targets_after, params, fix_branching=True, max_paths=None,
-                   return_fields=False, timings=None, soma=None, consume=None, scratch_scale=1, voxel_graph=None):
-        """Run find_root -> DAF -> PDRF -> path loop for the connected components `segids`.
+    def trace_flags(self, ghosts, pool, voxel_graph, big=False, fused=False):
+        """the flag word of one kh_trace_paths launch (KH_TRACE_* of include/kimi_hip.h); big: the second-stream launch of the
+        largest labels, which may keep heap chunks in LDS and have a thread count of its own"""
+        A = _abi
+        big_ok = self.trace_threads == 256 if self.big_lds_labels is None else True
+        on = ((A.TRACE_PROFILE, self.profile), (A.TRACE_HEAP_PRIO, self.heap_prio), (A.TRACE_NO_GHOSTS, not ghosts),
+              (A.TRACE_GHOST_PARANOID, ghosts and self.ghost_paranoid), (A.TRACE_BIG_LDS_HEAP, big and self.big_lds_heap and big_ok),
+              (A.TRACE_SCRATCH_POOL, pool), (A.TRACE_FUSED_EDF, fused), (A.TRACE_VOXEL_GRAPH, voxel_graph))
+        threads = self.big_threads if big and self.big_threads else self.trace_threads
+        return sum(flag for flag, yes in on if yes) | {64: A.TRACE_THREADS_64, 128: A.TRACE_THREADS_128}.get(threads, 0)
 
-        segids/counts/...: host arrays indexed by position (same order).  roots: array of linear indices or
-        NONE32.  targets_before/after: list (per label) of lists of linear indices (LIFO stacks as in
-        kimimaro/trace.py:225-228).  Returns a dict with per-label path arrays -- or, when `consume` is given,
-        hands such dicts (one per group of labels, as the groups finish) to `consume` and returns None.
+    def edf_mode(self, mode):
+        """the mode word of kh_edf_batch: 1 = find_root, 2 = DAF, with the threads per label above the low byte"""
+        return mode | (self.edf_threads << 8)
+
+    def run_labels(self, d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels, labels, params, fix_branching=True, max_paths=None,
+                   return_fields=False, timings=None, consume=None, scratch_scale=1, voxel_graph=None):
+        """Run find_root -> DAF -> PDRF -> path loop for the connected components `labels` (kimimaro_amd.plan.LabelSet: host
+        columns indexed by position, the roots as linear indices or NONE32, the target lists).  Returns a dict with per-label
+        path arrays -- or, when `consume` is given, hands such dicts (one per group of labels, as the groups finish) to
+        `consume` and returns None.  A label whose scratch overflowed is traced again in a launch of its own: its task record
+        (in "tasks" and last_tasks) is then the retry's, so its offsets and capacities refer to that launch's buffers, not to the
+        first plan's -- find a label's paths through voff / loff, never through the record's offsets.
         """
-        t = self.torch
-        lib = self.lib
-        st = self.stream()
-        sx, sy, sz = shape
-        nvox = sx * sy * sz
-        nl = len(segids)
-        if nl == 0:
+        if len(labels) == 0:
             return {"order": np.zeros(0, np.int64), "tasks": np.zeros(0, _abi.LABEL_T), "paths": []}
-        segids = np.asarray(segids, dtype=np.int64)
-        counts = np.asarray(counts, dtype=np.int64)
-        if consume is not None and nl > 1:
-            # more per-label scratch than the budget: several launches, each over a group of labels that fits
-            groups = plan_launches(counts, self.scratch_budget)
-            if len(groups) > 1:
-                done, retried = [], 0
-                pick_list = lambda a, g: [a[i] for i in g] if a is not None else None
-                for g in groups:
-                    g = np.asarray(g, dtype=np.int64)
-                    sub_soma = None if soma is None else {k: np.asarray(v)[g] for k, v in soma.items()}
-                    self.run_labels(d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels, segids[g], counts[g],
-                                    np.asarray(dbf_max)[g], np.asarray(first_index)[g], np.asarray(xmin)[g],
-                                    np.asarray(xmax)[g], np.asarray(roots, dtype=np.uint32)[g], pick_list(targets_before, g),
-                                    pick_list(targets_after, g), params, fix_branching=fix_branching, max_paths=max_paths,
-                                    timings=timings, soma=sub_soma, consume=consume,
-                                    scratch_scale=scratch_scale, voxel_graph=voxel_graph)
-                    done.append(self.last_tasks)
-                    retried += self.last_retries
-                self.last_tasks = np.concatenate(done)
-                self.last_retries = retried           # (each nested call resets it: accumulate over the groups)
-                return None
-        order = np.argsort(-counts, kind="stable")  # big labels first: their workgroups start first
-        slot_of_label = -np.ones(nlabels + 1, dtype=np.int32)
-        slot_of_label[segids[order]] = np.arange(nl, dtype=np.int32)
+        volume = (d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels)
+        opts = SimpleNamespace(fix_branching=fix_branching, max_paths=max_paths, return_fields=return_fields, timings=timings,
+                               scratch_scale=scratch_scale, voxel_graph=voxel_graph, streaming=consume is not None)
+        # with a sink: more per-label scratch than the budget means several launches, each over a group of labels that fits;
+        # without one (single labels, tests): one group, whose dicts -- first attempt, retries -- are kept and merged by label
+        groups = plan_launches(labels.count, self.scratch_budget) if consume is not None and len(labels) > 1 else [None]
+        parts, done, retried = [], [], 0
+        for g in groups:
+            run = self._trace_group(volume, labels if len(groups) == 1 else labels.take(g), params, consume or parts.append, opts)
+            done.append(self.last_tasks)
+            retried += self.last_retries
+        self.last_tasks = np.concatenate(done) if len(done) > 1 else done[0]
+        self.last_retries = retried           # (each group resets it: accumulate over the groups)
+        if consume is not None:
+            return None
+        res = _merge_groups(parts, self.last_tasks)
+        if return_fields:
+            res["daf"] = run.d_field[:run.nvox].cpu().numpy()
+            res["pdrf"] = run.b["pdrf"][:run.nvox].cpu().numpy()
+            res["alive"] = run.b["alive"].cpu().numpy()
+        return res
 
-        cnt = counts[order]
-        list_off = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64)
-        total = int(cnt.sum())
-        qcap = cnt + 64
-        q_off = np.concatenate([[0], np.cumsum(qcap)[:-1]]).astype(np.int64)
-        # heap / path scratch are sized for the common case; a label that overflows them is traced again on its own
-        # with `scratch_scale` times as much (below) -- the reference has no such limits
-        # heap: 3 nodes per voxel for small labels, 1.5 per voxel + 4096 for the others (the deepest heap of c3's largest
-        # label holds 0.7 nodes per voxel); never less than the sweep's lists need (11 / 8 nodes per voxel + 1536)
-        hbase = np.maximum((3 * cnt) // 2 + 4096, np.minimum(3 * cnt + 2048, 32768))
-        hcap = np.maximum(hbase * scratch_scale // self.scratch_divisor, 64)
-        h_off = np.concatenate([[0], np.cumsum(hcap)[:-1]]).astype(np.int64)
-        # path buffers: c3's labels write 527 vertices at most, 3 % of their voxels at most (round 5 kept 64 Ki entries for every label
-        # above 16 Ki voxels: 2 GB per volume); a label that needs more is traced again with `scratch_scale` x 8
-        pcap = np.maximum((cnt // 16 + 2048) * scratch_scale // self.scratch_divisor, 8)
-        # first attempt: heap and journal from a pool (engine.SCRATCH_POOL_FRACTION); retries and test runs with shrunk scratch: slices
-        use_pool = self.scratch_pool and scratch_scale == 1 and self.scratch_divisor == 1 and nl >= 4
-        p_off = np.concatenate([[0], np.cumsum(pcap)[:-1]]).astype(np.int64)
-        if max(total, int(qcap.sum()), int(hcap.sum()), int(pcap.sum())) >= 2 ** 32:
-            raise ValueError("kimimaro_amd: scratch offsets exceed 32 bits; shard the labels")
+    def _trace_group(self, volume, labels, params, sink, o):
+        """One group of labels that fits the scratch budget: plan -> allocate -> one of the two schedules -> retry of the labels
+        whose scratch overflowed.  Every result dict goes to `sink`; leaves the labels' final task records in last_tasks."""
+        d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels = volume
+        nl = len(labels)
+        order = label_order(labels.count)
+        rmax_t = sweep_radii(labels.dbf_max[order], params)
+        lv = self.sweep_levels(shape, anisotropy, rmax_t, labels.count[order]) if self.sweep else None
+        p = plan_tasks(labels, params, lv, order=order, rmax_t=rmax_t, nlabels=nlabels, max_paths=o.max_paths,
+                       scratch_scale=o.scratch_scale, scratch_divisor=self.scratch_divisor, scratch_pool=self.scratch_pool,
+                       scratch_pool_fraction=self.scratch_pool_fraction, window_cap=self.window_cap,
+                       window_cap_always=self.window_cap_always, arena_divisor=self.arena_divisor, lds_levels=self.sweep_lds_levels)
+        if p.sweep_on:
+            self.last_arena_bytes = p.ev_total * 256
+        # Who runs the searches (find_root, DAF) and the PDRF, decided once:
+        #   "fused"  each label's own workgroup, inside the path kernel (KH_TRACE_FUSED_EDF);
+        #   "before" batch launches over all labels in front of the path loop (return_fields, other exponents, fuse_edf off);
+        #   "early"  volumes in flight (`early_labels`, set by kimimaro_amd.lanes): the LARGEST labels are fused and go first, on a
+        #            second stream -- their chains, the heap emulation of a volume's large labels, seconds long, then start at once
+        #            instead of behind the searches of all labels; the rest keeps the batch kernels (70 VGPRs: twice the waves per
+        #            CU of the path kernel) on the lane's own stream, behind that launch.
+        can_fuse = _abi.is_pow2_exponent(params["pdrf_exponent"]) and not o.return_fields
+        early = int(min(self.early_labels, nl - 1)) if (can_fuse and o.streaming and self.early_labels > 0 and nl > 1) else 0
+        who = "early" if early > 0 else "fused" if can_fuse and self.fuse_edf else "before"
+        # tasks are sorted by size, so the biggest labels (the head of the run) are dispatched first; when the results
+        # are consumed incrementally they go to a second stream and the others are collected while they still run
+        slots = self.split_slots if self.big_lds_labels is None else self.big_lds_labels    # (big_lds_labels: also in a lane, whose split_slots is 0)
+        n_large = early if early > 0 else int(min(slots, np.count_nonzero(p.cnt >= self.split_min_voxels)))
 
-        tasks = np.zeros(nl, dtype=_abi.LABEL_T)
-        tasks["segid"] = segids[order]
-        tasks["list_offset"] = list_off
-        tasks["count"] = cnt
-        tasks["xmin"] = np.asarray(xmin)[order]
-        tasks["xmax"] = np.asarray(xmax)[order]
-        tasks["source"] = np.asarray(first_index)[order]
-        tasks["root"] = np.asarray(roots, dtype=np.uint32)[order]
-        f = np.float32
-        dm = np.asarray(dbf_max, dtype=np.float32)[order]
-        # M = f32(1 / dbf_max ** 1.01) with numpy scalar semantics, kimimaro/trace.py:335-336
-        tasks["M"] = np.array([f(1 / (f(v) ** 1.01)) if v > 0 else f(0) for v in dm], dtype=np.float32)
-        tasks["q_offset"] = q_off
-        tasks["q_capacity"] = qcap
-        tasks["heap_offset"] = h_off
-        tasks["heap_capacity"] = hcap
-        tasks["path_offset"] = p_off
-        tasks["path_capacity"] = pcap
-        tasks["max_paths"] = 0 if max_paths is None else int(max_paths)
-        if _abi.is_pow2_exponent(params["pdrf_exponent"]):     # KH_TRACE_FUSED_EDF: compute_pdrf's parameters travel with the task
-            tasks["pdrf_log2e"] = int(params["pdrf_exponent"]).bit_length() - 1
-            tasks["pdrf_scale"] = np.float32(params["pdrf_scale"])
-        if soma is not None:  # per label (caller order): soma_mode, fsr, soma_radius, soma_scale, soma_const
-            for key in ("soma_mode", "fsr", "soma_radius", "soma_scale", "soma_const"):
-                tasks[key] = np.asarray(soma[key])[order]
-        # order-free invalidation sweep: level table + per-label event arenas
-        d_rank, rdims, max_nlev = None, (0, 0, 0), 0
-        ev_total = 0
-        sweep_on = False
-        if self.sweep and nl > 0:
-            rmax_t = (np.float32(params["scale"]) * dm + np.float32(params["const"])).astype(np.float32)   # f32 ops as pyx:393-395
-            lv = self.sweep_levels(shape, anisotropy, rmax_t, cnt)
-            if lv is not None and int(lv["nlev"].max()) > 0:
-                nlev, win, ok = lv["nlev"], lv["win"], lv["ok"]
-                if self.window_cap and (self.window_cap_always or
-                                        np.count_nonzero(win > int(self.window_cap)) <= max(1, int(0.005 * win.size))):
-                    # (only when few labels pay for it: a capped label's widest calls are redone by the heap emulation)
-                    win = np.where(win > 0, np.minimum(win, int(self.window_cap)), win)
-                # fixed-size event chunks, chained per level (csrc/sweep.h): what is pending at one time
-                shift, chunks = plan_arena(cnt, nlev, True, win)
-                chunks = np.maximum(chunks // int(self.arena_divisor), 8)
-                in_lds = (win > 0) | (nlev <= self.sweep_lds_levels)   # the others: heap emulation only (the kernel decides the same)
-                # [spill table, 12 B per entry][(the free stack of rounds 4-5, 4 B per chunk: unused since round 6)][chunks]
-                spill = plan_spill(cnt)
-                units = np.where((nlev > 0) & in_lds, arena_units(chunks, shift, spill), 0)
-                ev_off = np.concatenate([[0], np.cumsum(units)[:-1]]).astype(np.int64)
-                ev_total = int(units.sum())
-                self.last_arena_bytes = ev_total * 256
-                if ev_total >= 2 ** 32:
-                    raise ValueError("kimimaro_amd: event arena offsets exceed 32 bits; shard the labels")
-                tasks["nlev"] = nlev
-                tasks["sweep_rmax"] = np.where(ok, rmax_t, 0).astype(np.float32)
-                tasks["ev_offset"] = ev_off
-                tasks["ev_chunks"] = np.where(nlev > 0, chunks, 0)
-                tasks["ev_shift"] = shift
-                tasks["ev_spill"] = np.where((nlev > 0) & in_lds, spill, 0)
-                tasks["lev_window"] = win
-                in_words = np.where(win > 0, win, np.where(in_lds, nlev, 0))     # LDS words each label wants
-                max_nlev = int(in_words.max()) if in_words.size else 0
-                d_rank, rdims = lv["d_rank"], lv["rdims"]
-                sweep_on = True
-        tgt = []
-        tgt_off = np.zeros(nl, dtype=np.int64)
-        for s, o in enumerate(order):
-            tgt_off[s] = len(tgt)
-            b = list(targets_before[o]) if targets_before is not None else []
-            a = list(targets_after[o]) if targets_after is not None else []
-            tasks["n_before"][s] = len(b)
-            tasks["n_after"][s] = len(a)
-            tgt.extend(b)
-            tgt.extend(a)
-        tasks["tgt_offset"] = tgt_off
-        tgt_arr = np.asarray(tgt + [0], dtype=np.uint32)
-
-        d_tasks = t.from_numpy(tasks.view(np.uint8).reshape(-1)).to(self.device)
-        d_slot = t.from_numpy(slot_of_label).to(self.device)
-        d_off = t.from_numpy(list_off.astype(np.uint32).view(np.int32)).to(self.device)
-        d_cur = self.empty(nl, t.int32)
-        d_lists = self.empty(max(total, 1), t.int32)
-        d_tgt = t.from_numpy(tgt_arr.view(np.int32)).to(self.device)
-        d_nbr = self.empty(nvox, t.int32)
-        d_queues = self.empty(4 * int(qcap.sum()), t.int32)
-        d_qstate = self.torch.zeros(nvox + 4, dtype=t.uint8, device=self.device)
-        P = self.ptr
-        wx, wy, wz = (float(anisotropy[0]), float(anisotropy[1]), float(anisotropy[2]))
-
-        def mark(name):
-            if timings is not None:
-                self.sync_stream()
-                import time
-                timings.append((name, time.perf_counter()))
-
-        mark("setup")
-        _abi.check(lib.kh_scatter_lists(P(d_cc), label_bytes, nvox, P(d_slot), nl, P(d_off), P(d_cur), P(d_lists), st))
-        _abi.check(lib.kh_neighbor_mask(P(d_cc), label_bytes, sx, sy, sz, P(d_nbr), st))
-        d_gate = None
-        if voxel_graph is not None:
-            # voxel_graph= of kimimaro.trace.trace (a u32 device volume, cc3d's bit layout): the directions a voxel's word does not
-            # allow leave the masks every search and the invalidation work from; d_gate = the corner entries at the x faces
-            d_gate = t.zeros(nvox + 4, dtype=t.uint8, device=self.device)
-            _abi.check(lib.kh_apply_voxel_graph(P(d_nbr), P(voxel_graph), nvox, P(d_gate), st))
-        mark("lists+nbrmask")
-        expo = params["pdrf_exponent"]
-        # The searches (find_root, DAF) and the PDRF either run inside the path kernel, by each label's own workgroup
-        # (KH_TRACE_FUSED_EDF), or as launches over the labels in front of it (`searches` below).  With volumes in flight
-        # (`early_labels`, set by kimimaro_amd.lanes) the LARGEST labels are fused and go first, on a second stream: their chains --
-        # the heap emulation of a volume's large labels, seconds long -- then start at once instead of behind the searches of all
-        # labels; the rest keeps the batch kernels (70 VGPRs: twice the waves per CU of the path kernel) on the lane's own stream.
-        can_fuse = _abi.is_pow2_exponent(expo) and not return_fields
-        early = int(min(self.early_labels, nl - 1)) if (can_fuse and consume is not None and self.early_labels > 0 and nl > 1) else 0
-        fuse_rest = can_fuse and self.fuse_edf and early == 0
-        d_ldaf = self.empty(max(total, 1), t.float32)
-        d_pdrf = self.empty(nvox + 4, t.float32)
-        fields = {"d_field": None}
-
-        def searches(first, count):
-            """find_root + DAF + PDRF of the task slots [first, first + count) as batch launches on the current stream"""
-            if count <= 0:
-                return
-            if fields["d_field"] is None:
-                fields["d_field"] = self.empty(nvox + 4, t.float32)
-            d_field = fields["d_field"]
-            _searches_launch(first, count, d_field)
-            if not return_fields:
-                fields["d_field"] = None     # the DAF lives on in list order (d_ldaf); its volume goes back to the pool
-
-        def _searches_launch(first, count, d_field):
-            tasks_ptr = C.c_void_p(d_tasks.data_ptr() + first * _abi.LABEL_T.itemsize)
-            lo = int(list_off[first])
-            n_list = int(cnt[first:first + count].sum())
-            lists_ptr = C.c_void_p(d_lists.data_ptr() + 4 * lo)
-            ldaf_ptr = C.c_void_p(d_ldaf.data_ptr() + 4 * lo)
-            d_slot_use, keep = d_slot, 0
-            if first > 0 or first + count < nl:
-                # only these labels: the others' voxels are left alone (they are another launch's business)
-                sl = slot_of_label.copy()
-                sl[segids[order][:first]] = -1
-                sl[segids[order][first + count:]] = -1
-                d_slot_use, keep = t.from_numpy(sl).to(self.device), _abi.PDRF_KEEP_OTHERS
-            # find_root (trace.py:291-308) then DAF (trace.py:139-145)
-            _abi.check(lib.kh_edf_batch(tasks_ptr, count, 1 | (self.edf_threads << 8), P(d_lists), P(d_nbr), sx, sy, sz, wx, wy, wz, P(d_field), P(d_qstate), P(d_queues), st))
-            mark("edf_root")
-            _abi.check(lib.kh_edf_batch(tasks_ptr, count, 2 | (self.edf_threads << 8), P(d_lists), P(d_nbr), sx, sy, sz, wx, wy, wz, P(d_field), P(d_qstate), P(d_queues), st))
-            mark("edf_daf")
-            _abi.check(lib.kh_gather_f32(P(d_field), lists_ptr, n_list, ldaf_ptr, st))
-            # PDRF (trace.py:148)
-            pdrf_call = lambda stage: _abi.check(lib.kh_pdrf(P(d_cc), label_bytes, nvox, P(d_slot_use), P(d_tasks), P(d_dbf), P(d_field),
-                                                             stage | keep if stage >= 0 else stage, np.float32(params["pdrf_scale"]),
-                                                             P(d_pdrf), st))
-            if _abi.is_pow2_exponent(expo):
-                pdrf_call(int(expo).bit_length() - 1)          # repeated squaring, trace.py:343-345
-            else:
-                # trace.py:346-347: np.power.  Its rounding is the host numpy's (libm / SVML powf), which no device powf can
-                # promise, so exactly that function is applied -- by numpy itself -- between the two device halves.
-                # Only the selected labels' voxels make the trip (their list is on the device already): gathered into a compact
-                # array, raised on the host, scattered back -- 8 B per foreground voxel instead of 8 B per voxel of the volume.
-                pdrf_call(_abi.PDRF_BASE)
-                d_base = self.empty(max(total, 1), t.float32)
-                _abi.check(lib.kh_gather_f32(P(d_pdrf), P(d_lists), total, P(d_base), st))
-                base = d_base[:total].cpu().numpy()
-                with np.errstate(all="ignore"):
-                    np.power(base, expo, out=base)
-                idx = d_lists[:total].to(t.int64) & 0xFFFFFFFF       # u32 linear indices kept in an int32 tensor
-                d_pdrf.index_copy_(0, idx, t.from_numpy(base).to(self.device))
-                pdrf_call(_abi.PDRF_FINISH)
-            mark("pdrf")
-
-        searched = False
-        if early == 0 and not fuse_rest:
-            searches(0, nl)          # (before the path loop's own volumes are allocated: the DAF volume's block serves them afterwards)
-            searched = True
-        d_dist = self.empty(nvox + 4, t.float32)     # (+ padding: the searches read rows of three words)
-        _abi.check(lib.kh_fill_f32(P(d_dist), nvox + 4, float("inf"), st))
-        d_alive = self.empty(nvox, t.uint8)
-        _abi.check(lib.kh_init_alive(P(d_cc), label_bytes, nvox, P(d_slot), P(d_alive), st))
-        jnodes = (2 * qcap + 3) // 4                        # a label's ghost journal in 16-byte nodes
-        if use_pool:
-            frac = float(self.scratch_pool_fraction)
-            pool_nodes = int(max(frac * float((hcap + jnodes).sum()), (2 if frac >= 0.05 else 0) * float((hcap + jnodes).max()))) + 1
-            pool_nodes = min(pool_nodes, 2 ** 32 - 2)
-            d_heap = self.empty(2 * pool_nodes, t.int64)   # 16-byte nodes; node 0 = {handed out, capacity}
-            d_heap[:2] = t.from_numpy(np.array([1, pool_nodes, 0, 0], dtype=np.uint32).view(np.int64)).to(self.device)
+        run = _LabelRun(self, volume, labels, params, p, lv, o)
+        run.allocate_inputs()
+        if who == "before":
+            run.searches(0, nl)          # (before the path loop's own volumes are allocated: the DAF volume's block serves them afterwards)
+        run.allocate_path_scratch()
+        self.last_retries = 0
+        if o.streaming and 0 < n_large < nl:
+            records = run.split_schedule(n_large, who, sink)
         else:
-            d_heap = self.empty(2 * int(hcap.sum()), t.int64)  # 16-byte nodes
-        d_cstate = t.zeros(nvox if sweep_on else 1, dtype=t.int64, device=self.device)
-        d_sched = self.sched_volume(nvox) if sweep_on else None
-        d_arena = self.empty(max(ev_total, 1) * 32 + 32, t.int64)   # units of 256 bytes, 256-byte aligned start
-        arena_ptr = C.c_void_p((d_arena.data_ptr() + 255) & ~255)
-        d_pverts = self.empty(int(pcap.sum()), t.int32)
-        d_plens = self.empty(int(pcap.sum()), t.int32)
+            records = run.single_schedule(who, sink)
+        if run.retry:
+            # the labels whose scratch overflowed, again with 8 x as much; their dicts go to the sink like every other and
+            # their records -- the good attempt's status bits and statistics -- take the place of the failed attempt's
+            nretry = len(run.retry)
+            again = SimpleNamespace(**{**vars(o), "scratch_scale": o.scratch_scale * 8, "timings": None, "return_fields": False})
+            self._trace_group(volume, labels.take(run.retry), params, sink, again)
+            self.last_retries = nretry + self.last_retries      # (the nested call counted its own)
+            pos = {int(sid): i for i, sid in enumerate(records["segid"])}
+            for rec in self.last_tasks:
+                records[pos[int(rec["segid"])]] = rec
+        self.last_tasks = records
+        return run
+
+
+def _merge_groups(parts, records):
+    """One result dict from the dicts a call without a sink produced: the first attempt over all labels, then the retries, whose
+    labels' paths replace the failed attempt's (matched by component id); `records`: the labels' final task records."""
+    res = parts[0]
+    if len(parts) > 1:
+        cut = lambda d, key, off, s: d[key][d[off][s]:d[off][s + 1]]
+        pos = {int(sid): s for s, sid in enumerate(res["tasks"]["segid"])}
+        per = {key: [cut(res, key, off, s) for s in range(len(pos))] for key, off in (("verts", "voff"), ("radii", "voff"), ("lens", "loff"))}
+        for sub in parts[1:]:
+            for s2, sid in enumerate(sub["tasks"]["segid"]):
+                for key, off in (("verts", "voff"), ("radii", "voff"), ("lens", "loff")):
+                    per[key][pos[int(sid)]] = cut(sub, key, off, s2)
+        for key in per:
+            res[key] = np.concatenate(per[key])
+        res["voff"] = np.concatenate([[0], np.cumsum([len(v) for v in per["verts"]])])
+        res["loff"] = np.concatenate([[0], np.cumsum([len(v) for v in per["lens"]])])
+    res["tasks"] = records
+    return res
+
+
+class _LabelRun:
+    """One launch plan of Engine.run_labels on the device: the plan (kimimaro_amd.plan.plan_tasks), the device buffers and the
+    call's options; the steps of the pipeline are its methods."""
+
+    def __init__(self, eng, volume, labels, params, plan, lv, o):
+        self.eng, self.lib, self.t = eng, eng.lib, eng.torch
+        self.d_cc, self.label_bytes, self.d_dbf, self.shape, anisotropy, _ = volume
+        self.nvox = self.shape[0] * self.shape[1] * self.shape[2]
+        self.w = (float(anisotropy[0]), float(anisotropy[1]), float(anisotropy[2]))
+        self.labels, self.params, self.p, self.o = labels, params, plan, o
+        self.nl = len(labels)
+        self.st = eng.stream()
+        self.timed = o.timings is not None or eng.time_kernels
+        self.d_rank, self.rdims = (lv["d_rank"], lv["rdims"]) if plan.sweep_on else (None, (0, 0, 0))
+        self.b = {}                # device buffers by name, in the order they were allocated
+        self.d_field = None        # the DAF volume of the batch searches (kept for return_fields only)
+        self.kernel_events = []    # (first, count, start, end, stream): HIP events around each path-loop launch (timings only)
+        self.retry = []            # positions (caller order) of the labels whose scratch overflowed
+
+    def mark(self, name):
+        if self.o.timings is not None:
+            self.eng.sync_stream()
+            import time
+            self.o.timings.append((name, time.perf_counter()))
+
+    def allocate_inputs(self):
+        """task records, voxel lists, neighbour masks and the work lists; then the two fields the searches fill"""
+        t, eng, lib, p, b, P = self.t, self.eng, self.lib, self.p, self.b, Engine.ptr
+        sx, sy, sz = self.shape
+        host = lambda a: t.from_numpy(a).to(eng.device)
+        b["tasks"] = host(p.tasks.view(np.uint8).reshape(-1))
+        b["slot"] = host(p.slot_of_label)
+        b["off"] = host(p.list_off.astype(np.uint32).view(np.int32))
+        b["cur"] = eng.empty(self.nl, t.int32)
+        b["lists"] = eng.empty(max(p.total, 1), t.int32)
+        b["tgt"] = host(p.tgt_arr.view(np.int32))
+        b["nbr"] = eng.empty(self.nvox, t.int32)
+        b["queues"] = eng.empty(4 * int(p.qcap.sum()), t.int32)
+        b["qstate"] = t.zeros(self.nvox + 4, dtype=t.uint8, device=eng.device)
+        self.mark("setup")
+        _abi.check(lib.kh_scatter_lists(P(self.d_cc), self.label_bytes, self.nvox, P(b["slot"]), self.nl, P(b["off"]), P(b["cur"]),
+                                        P(b["lists"]), self.st))
+        _abi.check(lib.kh_neighbor_mask(P(self.d_cc), self.label_bytes, sx, sy, sz, P(b["nbr"]), self.st))
+        b["gate"] = None
+        if self.o.voxel_graph is not None:
+            # voxel_graph= of kimimaro.trace.trace (a u32 device volume, cc3d's bit layout): the directions a voxel's word does not
+            # allow leave the masks every search and the invalidation work from; gate = the corner entries at the x faces
+            b["gate"] = t.zeros(self.nvox + 4, dtype=t.uint8, device=eng.device)
+            _abi.check(lib.kh_apply_voxel_graph(P(b["nbr"]), P(self.o.voxel_graph), self.nvox, P(b["gate"]), self.st))
+        self.mark("lists+nbrmask")
+        b["ldaf"] = eng.empty(max(p.total, 1), t.float32)
+        b["pdrf"] = eng.empty(self.nvox + 4, t.float32)
+
+    def allocate_path_scratch(self):
+        """the path loop's own volumes and per-label scratch (after the batch searches: their DAF volume's block is free again)"""
+        t, eng, lib, p, b, P = self.t, self.eng, self.lib, self.p, self.b, Engine.ptr
+        nvox = self.nvox
+        b["dist"] = eng.empty(nvox + 4, t.float32)     # (+ padding: the searches read rows of three words)
+        _abi.check(lib.kh_fill_f32(P(b["dist"]), nvox + 4, float("inf"), self.st))
+        b["alive"] = eng.empty(nvox, t.uint8)
+        _abi.check(lib.kh_init_alive(P(self.d_cc), self.label_bytes, nvox, P(b["slot"]), P(b["alive"]), self.st))
+        if p.use_pool:
+            b["heap"] = eng.empty(2 * p.pool_nodes, t.int64)   # 16-byte nodes; node 0 = {handed out, capacity}
+            b["heap"][:2] = t.from_numpy(np.array([1, p.pool_nodes, 0, 0], dtype=np.uint32).view(np.int64)).to(eng.device)
+        else:
+            b["heap"] = eng.empty(2 * int(p.hcap.sum()), t.int64)  # 16-byte nodes
+        b["cstate"] = t.zeros(nvox if p.sweep_on else 1, dtype=t.int64, device=eng.device)
+        b["sched"] = eng.sched_volume(nvox) if p.sweep_on else None
+        b["arena"] = eng.empty(max(p.ev_total, 1) * 32 + 32, t.int64)   # units of 256 bytes, 256-byte aligned start
+        self.arena_ptr = C.c_void_p((b["arena"].data_ptr() + 255) & ~255)
+        b["pverts"] = eng.empty(int(p.pcap.sum()), t.int32)
+        b["plens"] = eng.empty(int(p.pcap.sum()), t.int32)
         # ghosts: the journal of the voxels that changed since the call that made the first ghost (2 entries per voxel of a
         # label at most: made a ghost, killed) and the weights the path vertices had before they became rails
-        use_ghosts = self.ghosts and sweep_on
-        d_journal = self.empty(2 * int(qcap.sum()), t.int32) if use_ghosts and not use_pool else None
-        d_psave = self.empty(int(pcap.sum()), t.float32) if use_ghosts and fix_branching else None
-        if use_ghosts and not fix_branching:
-            d_psave = None
-        # tasks are sorted by size, so the biggest labels (the tail of the run) are dispatched first; when the results
-        # are consumed incrementally they go to a second stream and the others are collected while they still run
-        n_large = int(min(self.split_slots, np.count_nonzero(cnt >= self.split_min_voxels)))
-        if self.big_lds_labels is not None:     # (also in a lane, whose split_slots is 0: the lane then uses a second stream)
-            n_large = int(min(self.big_lds_labels, np.count_nonzero(cnt >= self.split_min_voxels)))
-        if early > 0:
-            n_large = early
-        # KH_TRACE_PROFILE | KH_TRACE_HEAP_PRIO | KH_TRACE_THREADS_64 / _128
-        # ... | KH_TRACE_NO_GHOSTS | KH_TRACE_GHOST_PARANOID
-        prof = (1 if self.profile else 0) | (2 if self.heap_prio else 0) | {64: 4, 128: 8}.get(self.trace_threads, 0) | \
-            (0 if use_ghosts else 16) | (32 if use_ghosts and self.ghost_paranoid else 0)
-        rank_ptr = P(d_rank) if d_rank is not None else C.c_void_p(0)
-        if not sweep_on:
-            rdims = (0, 0, 0)
-
+        self.use_ghosts = eng.ghosts and p.sweep_on
+        b["journal"] = eng.empty(2 * int(p.qcap.sum()), t.int32) if self.use_ghosts and not p.use_pool else None
+        b["psave"] = eng.empty(int(p.pcap.sum()), t.float32) if self.use_ghosts and self.o.fix_branching else None
         if os.environ.get("KH_DEBUG_ALLOC") == "1":      # developer knob: where every array of this call lives (to place a fault address)
-            for name, tt in (("tasks", d_tasks), ("lists", d_lists), ("nbr", d_nbr), ("queues", d_queues), ("qstate", d_qstate),
-                             ("ldaf", d_ldaf), ("pdrf", d_pdrf), ("dist", d_dist), ("alive", d_alive), ("heap", d_heap),
-                             ("cstate", d_cstate), ("sched", d_sched), ("arena", d_arena), ("pverts", d_pverts), ("plens", d_plens),
-                             ("journal", d_journal), ("psave", d_psave), ("dbf", d_dbf), ("cc", d_cc), ("tgt", d_tgt)):
+            for name, tt in list(b.items()) + [("dbf", self.d_dbf), ("cc", self.d_cc)]:
                 if tt is not None:
                     print("KHALLOC %-8s %#x .. %#x (%d B)" % (name, tt.data_ptr(), tt.data_ptr() + tt.numel() * tt.element_size(),
                                                              tt.numel() * tt.element_size()), file=sys.stderr, flush=True)
 
-        kernel_events = []     # (first, count, start, end): HIP events on the stream each path-loop launch went to (timings only)
+    def searches(self, first, count):
+        """find_root + DAF + PDRF of the task slots [first, first + count) as batch launches on the current stream"""
+        if count <= 0:
+            return
+        if self.d_field is None:
+            self.d_field = self.eng.empty(self.nvox + 4, self.t.float32)
+        self._batch_searches(first, count, self.d_field)
+        if not self.o.return_fields:
+            self.d_field = None     # the DAF lives on in list order (ldaf); its volume goes back to the pool
 
-        def launch(first, count, stream, tstream=None, big=False, fused=False):
-            tasks_ptr = C.c_void_p(d_tasks.data_ptr() + first * _abi.LABEL_T.itemsize)
-            big_ok = self.trace_threads == 256 if self.big_lds_labels is None else True
-            flags = prof | (64 if big and self.big_lds_heap and big_ok else 0) | (256 if use_pool else 0) | (512 if fused else 0)
-            # (KH_TRACE_BIG_LDS_HEAP, KH_TRACE_SCRATCH_POOL, KH_TRACE_FUSED_EDF)
-            if big and self.big_threads:          # the second-stream launch with a thread count of its own
-                flags = (flags & ~12) | {64: 4, 128: 8}.get(self.big_threads, 0)
-            if timings is not None or self.time_kernels:
-                tstream = tstream if tstream is not None else t.cuda.current_stream(self.device)
-                ev0, ev1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
-                ev0.record(tstream)
-                kernel_events.append((first, count, ev0, ev1, tstream))
-            _abi.check(lib.kh_trace_paths(tasks_ptr, count, P(d_lists), P(d_ldaf), P(d_nbr), sx, sy, sz, wx, wy, wz,
-                                          P(d_dbf), P(d_pdrf), P(d_dist), P(d_alive), P(d_qstate), P(d_tgt),
-                                          np.float32(params["scale"]), np.float32(params["const"]), P(d_queues), P(d_heap),
-                                          P(d_pverts), P(d_plens), rank_ptr, rdims[0], rdims[1], rdims[2], max_nlev,
-                                          P(d_cstate), self.sched_ptr(d_sched), arena_ptr, self.optr(d_journal), self.optr(d_psave),
-                                          self.optr(d_gate), flags | (128 if d_gate is not None else 0), int(bool(fix_branching)), stream))
-            if timings is not None or self.time_kernels:
-                kernel_events[-1][3].record(kernel_events[-1][4])
+    def _batch_searches(self, first, count, d_field):
+        t, eng, lib, p, b, P, st = self.t, self.eng, self.lib, self.p, self.b, Engine.ptr, self.st
+        (sx, sy, sz), (wx, wy, wz), nvox, expo = self.shape, self.w, self.nvox, self.params["pdrf_exponent"]
+        tasks_ptr = C.c_void_p(b["tasks"].data_ptr() + first * _abi.LABEL_T.itemsize)
+        lo = int(p.list_off[first])
+        n_list = int(p.cnt[first:first + count].sum())
+        lists_ptr = C.c_void_p(b["lists"].data_ptr() + 4 * lo)
+        ldaf_ptr = C.c_void_p(b["ldaf"].data_ptr() + 4 * lo)
+        d_slot_use, keep = b["slot"], 0
+        if first > 0 or first + count < self.nl:
+            # only these labels: the others' voxels are left alone (they are another launch's business)
+            sl = p.slot_of_label.copy()
+            sl[p.tasks["segid"][:first]] = -1
+            sl[p.tasks["segid"][first + count:]] = -1
+            d_slot_use, keep = t.from_numpy(sl).to(eng.device), _abi.PDRF_KEEP_OTHERS
+        # find_root (trace.py:291-308) then DAF (trace.py:139-145)
+        for mode, name in ((1, "edf_root"), (2, "edf_daf")):
+            _abi.check(lib.kh_edf_batch(tasks_ptr, count, eng.edf_mode(mode), P(b["lists"]), P(b["nbr"]), sx, sy, sz, wx, wy, wz,
+                                        P(d_field), P(b["qstate"]), P(b["queues"]), st))
+            self.mark(name)
+        _abi.check(lib.kh_gather_f32(P(d_field), lists_ptr, n_list, ldaf_ptr, st))
+        # PDRF (trace.py:148)
+        pdrf_call = lambda stage: _abi.check(lib.kh_pdrf(P(self.d_cc), self.label_bytes, nvox, P(d_slot_use), P(b["tasks"]), P(self.d_dbf),
+                                                         P(d_field), stage | keep if stage >= 0 else stage,
+                                                         np.float32(self.params["pdrf_scale"]), P(b["pdrf"]), st))
+        if _abi.is_pow2_exponent(expo):
+            pdrf_call(int(expo).bit_length() - 1)          # repeated squaring, trace.py:343-345
+        else:
+            # trace.py:346-347: np.power.  Its rounding is the host numpy's (libm / SVML powf), which no device powf can
+            # promise, so exactly that function is applied -- by numpy itself -- between the two device halves.
+            # Only the selected labels' voxels make the trip (their list is on the device already): gathered into a compact
+            # array, raised on the host, scattered back -- 8 B per foreground voxel instead of 8 B per voxel of the volume.
+            pdrf_call(_abi.PDRF_BASE)
+            d_base = eng.empty(max(p.total, 1), t.float32)
+            _abi.check(lib.kh_gather_f32(P(b["pdrf"]), P(b["lists"]), p.total, P(d_base), st))
+            base = d_base[:p.total].cpu().numpy()
+            with np.errstate(all="ignore"):
+                np.power(base, expo, out=base)
+            idx = b["lists"][:p.total].to(t.int64) & 0xFFFFFFFF       # u32 linear indices kept in an int32 tensor
+            b["pdrf"].index_copy_(0, idx, t.from_numpy(base).to(eng.device))
+            pdrf_call(_abi.PDRF_FINISH)
+        self.mark("pdrf")
 
-        def kernel_times():
-            """milliseconds of each path-loop launch of this call, from HIP events on the launch's own stream"""
-            self.last_path_kernel_ms = [(c, e0.elapsed_time(e1)) for _, c, e0, e1, _ in kernel_events]
-            # the span of the path phase: first start to last end over the (overlapped) launches of this call
-            first = min(kernel_events, key=lambda k: -min(k[2].elapsed_time(o[2]) for o in kernel_events))[2] if kernel_events else None
-            self.last_path_span_ms = max((first.elapsed_time(e1) for _, _, _, e1, _ in kernel_events), default=0.0) if first else 0.0
+    def launch(self, first, count, stream, tstream=None, big=False, fused=False):
+        """the path loop of the task slots [first, first + count) on `stream` (tstream: its torch object, for the HIP events)"""
+        t, eng, b, P, O = self.t, self.eng, self.b, Engine.ptr, Engine.optr
+        (sx, sy, sz), (wx, wy, wz), rdims = self.shape, self.w, self.rdims
+        tasks_ptr = C.c_void_p(b["tasks"].data_ptr() + first * _abi.LABEL_T.itemsize)
+        flags = eng.trace_flags(self.use_ghosts, self.p.use_pool, b["gate"] is not None, big=big, fused=fused)
+        if self.timed:
+            tstream = tstream if tstream is not None else t.cuda.current_stream(eng.device)
+            ev0, ev1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            ev0.record(tstream)
+            self.kernel_events.append((first, count, ev0, ev1, tstream))
+        _abi.check(self.lib.kh_trace_paths(tasks_ptr, count, P(b["lists"]), P(b["ldaf"]), P(b["nbr"]), sx, sy, sz, wx, wy, wz,
+                                           P(self.d_dbf), P(b["pdrf"]), P(b["dist"]), P(b["alive"]), P(b["qstate"]), P(b["tgt"]),
+                                           np.float32(self.params["scale"]), np.float32(self.params["const"]), P(b["queues"]),
+                                           P(b["heap"]), P(b["pverts"]), P(b["plens"]), O(self.d_rank), rdims[0], rdims[1], rdims[2],
+                                           self.p.max_nlev, P(b["cstate"]), eng.sched_ptr(b["sched"]), self.arena_ptr, O(b["journal"]),
+                                           O(b["psave"]), O(b["gate"]), flags, int(bool(self.o.fix_branching)), stream))
+        if self.timed:
+            ev1.record(tstream)
 
-        def collect(lo, hi):
-            """results of task slots [lo, hi) (device -> host on the current stream)."""
-            isz = _abi.LABEL_T.itemsize
-            part = d_tasks[lo * isz:hi * isz].cpu().numpy().view(_abi.LABEL_T).copy()
-            overflow = (part["status"] & 7) != 0          # work list / heap / path buffer too small: traced again below
-            bad = np.flatnonzero((part["status"] & ~np.uint32(7)) != 0)
-            if bad.size or (overflow.any() and scratch_scale >= 64):
-                s = int(bad[0]) if bad.size else int(np.flatnonzero(overflow)[0])
-                raise _abi.KimiHipError("label %d (cc id): %s" % (int(part["segid"][s]),
-                                                                   _abi.describe_status(int(part["status"][s]))))
-            for s in np.flatnonzero(overflow):
-                retry.append(int(order[lo + s]))
-                part["n_vertices"][s] = 0
-                part["n_paths"][s] = 0
-            # gather the used part of the path buffers: build a flat index on the host (small), gather on device
-            nverts = part["n_vertices"].astype(np.int64)
-            npaths = part["n_paths"].astype(np.int64)
-            def ranges(starts, counts):
-                """concatenation of starts[s] + arange(counts[s]) over s, without a Python loop"""
-                total = int(counts.sum())
-                before = np.cumsum(counts) - counts
-                return np.repeat(starts - before, counts) + np.arange(total, dtype=np.int64)
-            vidx = ranges(p_off[lo:hi].astype(np.int64), nverts)
-            lidx = ranges(p_off[lo:hi].astype(np.int64), npaths)
-            d_vidx = t.from_numpy(vidx).to(self.device)
-            d_lidx = t.from_numpy(lidx).to(self.device)
-            verts_dev = d_pverts[d_vidx]
-            verts = verts_dev.cpu().numpy().view(np.uint32)
-            lens = d_plens[d_lidx].cpu().numpy().view(np.uint32)
-            d_radii = self.empty(max(verts.size, 1), t.float32)
-            if verts.size:
-                _abi.check(lib.kh_gather_f32(P(d_dbf), P(verts_dev.contiguous()), verts.size, P(d_radii), self.stream()))
-            radii = d_radii.cpu().numpy()[: verts.size]
-            return {"order": order[lo:hi], "tasks": part, "verts": verts, "radii": radii, "lens": lens,
-                    "voff": np.concatenate([[0], np.cumsum(nverts)]), "loff": np.concatenate([[0], np.cumsum(npaths)])}
+    def kernel_times(self):
+        """milliseconds of each path-loop launch of this call, from HIP events on the launch's own stream"""
+        ke = self.kernel_events
+        self.eng.last_path_kernel_ms = [(c, e0.elapsed_time(e1)) for _, c, e0, e1, _ in ke]
+        # the span of the path phase: first start to last end over the (overlapped) launches of this call
+        first = min(ke, key=lambda k: -min(k[2].elapsed_time(o[2]) for o in ke))[2] if ke else None
+        self.eng.last_path_span_ms = max((first.elapsed_time(e1) for _, _, _, e1, _ in ke), default=0.0) if first else 0.0
 
-        retry = []   # positions (caller order) of the labels whose scratch overflowed
-        self.last_retries = 0
+    def collect(self, lo, hi):
+        """results of task slots [lo, hi) (device -> host on the current stream)."""
+        t, eng, b, P = self.t, self.eng, self.b, Engine.ptr
+        isz = _abi.LABEL_T.itemsize
+        part = b["tasks"][lo * isz:hi * isz].cpu().numpy().view(_abi.LABEL_T).copy()
+        overflow = (part["status"] & 7) != 0          # work list / heap / path buffer too small: traced again (Engine._trace_group)
+        bad = np.flatnonzero((part["status"] & ~np.uint32(7)) != 0)
+        if bad.size or (overflow.any() and self.o.scratch_scale >= 64):
+            s = int(bad[0]) if bad.size else int(np.flatnonzero(overflow)[0])
+            raise _abi.KimiHipError("label %d (cc id): %s" % (int(part["segid"][s]),
+                                                               _abi.describe_status(int(part["status"][s]))))
+        for s in np.flatnonzero(overflow):
+            self.retry.append(int(self.p.order[lo + s]))
+            part["n_vertices"][s] = 0
+            part["n_paths"][s] = 0
+        # gather the used part of the path buffers: build a flat index on the host (small), gather on device
+        nverts = part["n_vertices"].astype(np.int64)
+        npaths = part["n_paths"].astype(np.int64)
 
-        def run_retry(sink):
-            """re-trace the overflowed labels with 8x the scratch.  sink = None: returns the nested call's own (already
-            spliced) result, whose `order` indexes `retry`; else the groups go to `sink` like every other result."""
-            if not retry:
-                return None
-            nretry = len(retry)
-            pick = np.asarray(retry, dtype=np.int64)
-            sub = lambda a: [a[i] for i in pick] if a is not None else None
-            subsoma = None if soma is None else {k: np.asarray(v)[pick] for k, v in soma.items()}
-            got = self.run_labels(d_cc, label_bytes, d_dbf, shape, anisotropy, nlabels, segids[pick], counts[pick],
-                                  np.asarray(dbf_max)[pick], np.asarray(first_index)[pick], np.asarray(xmin)[pick],
-                                  np.asarray(xmax)[pick], np.asarray(roots, dtype=np.uint32)[pick], sub(targets_before),
-                                  sub(targets_after), params, fix_branching=fix_branching, max_paths=max_paths, soma=subsoma,
-                                  consume=sink, scratch_scale=scratch_scale * 8, voxel_graph=voxel_graph)
-            self.last_retries = nretry + self.last_retries      # (the nested call counted its own)
-            return got
+        def ranges(starts, counts):
+            """concatenation of starts[s] + arange(counts[s]) over s, without a Python loop"""
+            total = int(counts.sum())
+            before = np.cumsum(counts) - counts
+            return np.repeat(starts - before, counts) + np.arange(total, dtype=np.int64)
+        p_off = self.p.p_off[lo:hi].astype(np.int64)
+        d_vidx = t.from_numpy(ranges(p_off, nverts)).to(eng.device)
+        d_lidx = t.from_numpy(ranges(p_off, npaths)).to(eng.device)
+        verts_dev = b["pverts"][d_vidx]
+        verts = verts_dev.cpu().numpy().view(np.uint32)
+        lens = b["plens"][d_lidx].cpu().numpy().view(np.uint32)
+        d_radii = eng.empty(max(verts.size, 1), t.float32)
+        if verts.size:
+            _abi.check(self.lib.kh_gather_f32(P(self.d_dbf), P(verts_dev.contiguous()), verts.size, P(d_radii), eng.stream()))
+        radii = d_radii.cpu().numpy()[: verts.size]
+        return {"order": self.p.order[lo:hi], "tasks": part, "verts": verts, "radii": radii, "lens": lens,
+                "voff": np.concatenate([[0], np.cumsum(nverts)]), "loff": np.concatenate([[0], np.cumsum(npaths)])}
 
-        def splice_retried(records):
-            """consume paths: re-trace the overflowed labels (their groups go to `consume`) and put the nested call's records
-            -- the good attempt's status bits and statistics -- in the place of the failed attempt's."""
-            if not retry:
-                return records
-            run_retry(consume)
-            pos = {int(sid): i for i, sid in enumerate(records["segid"])}
-            for rec in self.last_tasks:
-                records[pos[int(rec["segid"])]] = rec
-            return records
+    def split_schedule(self, n_large, who, sink):
+        """The largest labels are the head of the run.  They go to a second stream (as large-LDS workgroups); the rest runs
+        on the caller's stream and its results are copied back and handed to `sink` (the Skeleton assembly on the host)
+        while the big labels are still being traced.  Returns the task records of all labels."""
+        t, eng, nl = self.t, self.eng, self.nl
+        cur = t.cuda.current_stream(eng.device)
+        if eng._side is None:
+            eng._side = t.cuda.Stream(device=eng.device)
+        side = eng._side
+        side.wait_stream(cur)
+        self.launch(0, n_large, C.c_void_p(side.cuda_stream), side, big=(who != "early"), fused=(who != "before"))
+        try:
+            if who == "early":
+                self.searches(n_large, nl - n_large)
+            self.launch(n_large, nl - n_large, self.st, fused=(who == "fused"))
+            small = self.collect(n_large, nl)
+            sink(small)                     # overlaps the big labels' kernel: no device-wide sync in here
+        finally:
+            cur.wait_stream(side)           # the scratch of this call must outlive the side stream's kernel
+            if sys.exc_info()[0] is not None:
+                side.synchronize()
+        big = self.collect(0, n_large)
+        self.mark("paths")
+        if self.timed:
+            self.kernel_times()
+        sink(big)
+        self.mark("d2h")
+        return np.concatenate([big["tasks"], small["tasks"]])
 
-        if consume is not None and 0 < n_large < nl:
-            # The largest labels are the tail of the run.  They go to a second stream (as large-LDS workgroups); the
-            # rest runs on the caller's stream and its results are copied back and handed to `consume` (the Skeleton
-            # assembly on the host) while the big labels are still being traced.
-            cur = t.cuda.current_stream(self.device)
-            if self._side is None:
-                self._side = t.cuda.Stream(device=self.device)
-            if not (fuse_rest or early > 0 or searched):
-                searches(0, nl)                 # (no fusion at all: every label's searches before either launch)
-            self._side.wait_stream(cur)
-            launch(0, n_large, C.c_void_p(self._side.cuda_stream), self._side, big=(early == 0), fused=(fuse_rest or early > 0))
-            try:
-                if early > 0:
-                    searches(n_large, nl - n_large)
-                launch(n_large, nl - n_large, st, fused=fuse_rest)
-                small = collect(n_large, nl)
-                consume(small)                  # overlaps the big labels' kernel: no device-wide sync in here
-            finally:
-                cur.wait_stream(self._side)     # the scratch of this call must outlive the side stream's kernel
-                if sys.exc_info()[0] is not None:
-                    self._side.synchronize()
-            big = collect(0, n_large)
-            mark("paths")
-            if timings is not None or self.time_kernels:
-                kernel_times()
-            consume(big)
-            mark("d2h")
-            self.last_tasks = splice_retried(np.concatenate([big["tasks"], small["tasks"]]))
-            return None
-        if not fuse_rest and not searched:
-            searches(0, nl)
-        if self.path_gate is not None and consume is not None:
-            self.sync_stream()
-            self.path_gate()
-        launch(0, nl, st, fused=fuse_rest)
-        mark("paths")
-        res = collect(0, nl)                  # (its device -> host copies wait for the launch)
-        if timings is not None or self.time_kernels:
-            kernel_times()
-        mark("d2h")
-        if consume is not None:
-            consume(res)
-            self.last_tasks = splice_retried(res["tasks"])
-            return None
-        if retry:
-            # splice the re-traced labels into the result (callers without a sink: single labels, tests)
-            # (the nested call splices its own further retries before it returns: one dict, `order` indexing `retry`)
-            redo = [run_retry(None)]
-            pos_of = {int(o): s for s, o in enumerate(res["order"])}
-            per_v = [res["verts"][res["voff"][s]:res["voff"][s + 1]] for s in range(nl)]
-            per_r = [res["radii"][res["voff"][s]:res["voff"][s + 1]] for s in range(nl)]
-            per_l = [res["lens"][res["loff"][s]:res["loff"][s + 1]] for s in range(nl)]
-            for sub in redo:
-                for s2, o2 in enumerate(sub["order"]):
-                    s = pos_of[retry[int(o2)]]
-                    per_v[s] = sub["verts"][sub["voff"][s2]:sub["voff"][s2 + 1]]
-                    per_r[s] = sub["radii"][sub["voff"][s2]:sub["voff"][s2 + 1]]
-                    per_l[s] = sub["lens"][sub["loff"][s2]:sub["loff"][s2 + 1]]
-                    for f in ("n_paths", "n_vertices", "status"):
-                        res["tasks"][f][s] = sub["tasks"][f][s2]
-            res["verts"] = np.concatenate(per_v) if per_v else res["verts"]
-            res["radii"] = np.concatenate(per_r) if per_r else res["radii"]
-            res["lens"] = np.concatenate(per_l) if per_l else res["lens"]
-            res["voff"] = np.concatenate([[0], np.cumsum([len(v) for v in per_v])])
-            res["loff"] = np.concatenate([[0], np.cumsum([len(v) for v in per_l])])
-        self.last_tasks = res["tasks"]
-        if return_fields:
-            res["daf"] = fields["d_field"][:nvox].cpu().numpy()
-            res["pdrf"] = d_pdrf[:nvox].cpu().numpy()
-            res["alive"] = d_alive.cpu().numpy()
-        return res
+    def single_schedule(self, who, sink):
+        """all labels in one launch on the caller's stream, behind the path gate.  Returns their task records."""
+        eng = self.eng
+        if eng.path_gate is not None and self.o.streaming:
+            eng.sync_stream()
+            eng.path_gate()
+        self.launch(0, self.nl, self.st, fused=(who == "fused"))
+        self.mark("paths")
+        res = self.collect(0, self.nl)                  # (its device -> host copies wait for the launch)
+        if self.timed:
+            self.kernel_times()
+        self.mark("d2h")
+        sink(res)
+        return res["tasks"]

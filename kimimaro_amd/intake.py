@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _abi
 from .engine import Engine, NONE32
+from .plan import LabelSet
 from .skeleton import Skeleton
 
 DEFAULT_TEASAR_PARAMS = {  # kimimaro/intake.py:47-56
@@ -561,11 +562,9 @@ def _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotrop
             eng._narrow = (None, eng._narrow[1])
     sel = np.asarray(segids, dtype=np.int64)
     asm = Assembler(shape, anisotropy, remapping)
-    eng.run_labels(d_lab, label_bytes, d_dbf, shape, anisotropy, nlabels, sel, counts[sel] if len(sel) else [],
-                         dbf_max[sel] if len(sel) else [], first_index[sel] if len(sel) else [],
-                         xmin[sel] if len(sel) else [], xmax[sel] if len(sel) else [], roots, tb, ta, params,
-                         fix_branching=fix_branching, max_paths=params.get("max_paths"), timings=timings, consume=asm.add,
-                         voxel_graph=d_graph)
+    labels = LabelSet(sel, counts[sel], dbf_max[sel], first_index[sel], xmin[sel], xmax[sel], roots, tb, ta)
+    eng.run_labels(d_lab, label_bytes, d_dbf, shape, anisotropy, nlabels, labels, params, fix_branching=fix_branching,
+                   max_paths=params.get("max_paths"), timings=timings, consume=asm.add, voxel_graph=d_graph)
     out = asm.finish()
     _mark("assemble")
     if soma_jobs:

@@ -31,6 +31,18 @@ def test_label_struct_matches_header():
     assert names == list(_abi.LABEL_T.names)
 
 
+def test_trace_flags_match_header():
+    """every KH_TRACE_* flag of the header has its twin in _abi, with the header's value"""
+    from kimimaro_amd import _abi
+    header = open(os.path.join(ROOT, "include", "kimi_hip.h")).read()
+    names = set(re.findall(r"^#define KH_(TRACE_\w+)", header, re.M))
+    defines = {name: int(value, 0) for name, value in re.findall(r"^#define KH_(TRACE_\w+)[ \t]+(\d+|0[xX][0-9a-fA-F]+)\b", header, re.M)}
+    assert len(names) >= 10 and names == set(defines), "KH_TRACE_* defines this test cannot read: %s" % sorted(names - set(defines))
+    for name, value in defines.items():
+        assert hasattr(_abi, name), "kimimaro_amd._abi lacks %s" % name
+        assert getattr(_abi, name) == value, name
+
+
 def test_product_fails_loudly_without_gpu():
     import numpy as np
     import torch
