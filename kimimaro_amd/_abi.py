@@ -22,6 +22,7 @@ SYMBOLS = [
     "kh_host_consolidate_paths",
     "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
     "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
+    "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel",
 ]
 
 
@@ -157,9 +158,14 @@ def lib():
     L.kh_nearest_label_voxels.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp]
     L.kh_binary_edge_count.argtypes = [vp, i64, C.c_uint32, vp, vp, vp, vp]
     L.kh_binary_edge_emit.argtypes = [vp, i64, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]
+    f64 = C.c_double
+    L.kh_cross_sections.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.kh_cross_sections_scratch_bytes.argtypes = [i64, i64, i64, i64]
+    L.kh_cross_sections_scratch_bytes.restype = i64
+    L.kh_host_section_voxel.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)
-        if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error",
+        if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",
                         "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths"):
             getattr(L, name).restype = ci
     _lib = L

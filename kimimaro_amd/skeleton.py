@@ -204,6 +204,84 @@ class Skeleton:
                                 skel.id, skel.transform, skel.space))
         return out
 
+    # -- traversal (osteoid's source is not available: PARITY UNPINNED, the orders below are DEFINED in DESIGN.md 3.12) ----
+    def _neighbours(self):
+        """the distinct neighbours of every vertex, ascending (self loops and repeated edges do not count)"""
+        n = self.vertices.shape[0]
+        e = np.asarray(self.edges, dtype=np.int64).reshape(-1, 2)
+        e = e[e[:, 0] != e[:, 1]]
+        both = np.unique(np.concatenate([e, e[:, ::-1]], axis=0), axis=0) if e.size else np.zeros((0, 2), dtype=np.int64)
+        starts = np.searchsorted(both[:, 0], np.arange(n + 1))
+        return [both[starts[i]:starts[i + 1], 1].tolist() for i in range(n)]
+
+    def _degrees(self):
+        return np.array([len(nb) for nb in self._neighbours()], dtype=np.int64)
+
+    def branches(self):
+        """indices of the vertices with three or more neighbours, ascending"""
+        return np.flatnonzero(self._degrees() >= 3)
+
+    def terminals(self):
+        """indices of the vertices with exactly one neighbour, ascending"""
+        return np.flatnonzero(self._degrees() == 1)
+
+    def paths(self, return_indices=False):
+        """The root-to-leaf paths of every connected component, as a list of (k, 3) vertex arrays (of index arrays with
+        return_indices).  Components come in the order of their smallest vertex; one of a single vertex has no path.  The root is the
+        vertex farthest in hops from the component's smallest vertex (the smallest index among equally far ones).  A depth-first
+        walk from the root takes neighbours in ascending index and skips visited ones (a cycle is cut where the walk closes it);
+        every vertex the walk cannot leave is a leaf and yields the path root .. leaf, in the order the leaves are reached -- paths
+        share their trunk."""
+        nbrs = self._neighbours()
+        n = len(nbrs)
+        seen = np.zeros(n, dtype=bool)
+        out = []
+        for start in range(n):
+            if seen[start] or not nbrs[start]:
+                seen[start] = True
+                continue
+            # breadth first from the smallest vertex: hops
+            hops = {start: 0}
+            level = [start]
+            while level:
+                nxt = []
+                for a in level:
+                    for b in nbrs[a]:
+                        if b not in hops:
+                            hops[b] = hops[a] + 1
+                            nxt.append(b)
+                level = nxt
+            far = max(hops.values())
+            root = min(v for v, h in hops.items() if h == far)
+            for v in hops:
+                seen[v] = True
+            visited = {root}
+            path = [root]
+            cursor = [0]                   # per vertex on the path: the next neighbour to look at
+            grew = [False]                 # ... and whether the walk went on from it
+            while path:
+                v = path[-1]
+                nb = nbrs[v]
+                k = cursor[-1]
+                while k < len(nb) and nb[k] in visited:
+                    k += 1
+                if k < len(nb):
+                    cursor[-1] = k + 1
+                    grew[-1] = True
+                    visited.add(nb[k])
+                    path.append(nb[k])
+                    cursor.append(0)
+                    grew.append(False)
+                    continue
+                if not grew[-1]:
+                    out.append(np.array(path, dtype=np.int64))
+                path.pop()
+                cursor.pop()
+                grew.pop()
+        if return_indices:
+            return out
+        return [self.vertices[p] for p in out]
+
     def to_swc(self):
         """SWC text (row f4, the format kimimaro_cli writes)."""
         n = self.vertices.shape[0]

@@ -1,4 +1,5 @@
-"""The analysis half of the reference's API that needs nothing from xs3d: kimimaro.oversegment (kimimaro/utility.py:562-644).
+"""The analysis half of the reference's API: kimimaro.oversegment (kimimaro/utility.py:562-644) and kimimaro.cross_sectional_area /
+cross_sectional_area_single (kimimaro/utility.py:168-560; further down).
 
 The reference walks the skeletons label by label, crops each label (shape_iterator, utility.py:114-166), asks dijkstra3d for the
 feature map of the distance field from the skeleton's vertices and adds the crops into one uint64 volume on the host.  Here the
@@ -8,14 +9,17 @@ PARITY UNPINNED, the result is defined order free."""
 from __future__ import annotations
 
 import copy
+import time
 
 import numpy as np
 
-from . import _abi, feature
+from . import _abi, feature, section
 from .intake import format_labels
 from .skeleton import Skeleton
 
 SEGMENTS_ATTRIBUTE = {"id": "segments", "data_type": "uint64", "num_components": 1}    # utility.py:583-587
+XS_PROP = {"id": "cross_sectional_area", "data_type": "float32", "num_components": 1}                # utility.py:23-27
+XS_CONTACT_PROP = {"id": "cross_sectional_area_contacts", "data_type": "uint8", "num_components": 1}  # utility.py:29-33
 
 
 def extract_skeleton_from_binary_image(image):
@@ -207,3 +211,259 @@ def oversegment(all_labels, skeletons, anisotropy=(1, 1, 1), progress=False, fil
     else:
         out = d_feat.cpu().numpy().view(np.uint32)
     return out.reshape(shape, order="F").reshape(shape0, order="F"), skeletons
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# kimimaro.cross_sectional_area (kimimaro/utility.py:168-560).  The reference crops every label, walks its skeleton's paths and asks
+# xs3d for one section per vertex, one after the other.  Here the whole volume stays in HBM and every (vertex, normal) pair of every
+# skeleton goes to the MI355X in one launch (kimimaro_amd.section, csrc/section.hip); the host only walks the paths.  xs3d and
+# osteoid are absent from the reference tree: PARITY UNPINNED, sections and path order are defined in DESIGN.md 3.12.
+
+def moving_average(a, n, mode="symmetric"):
+    """kimimaro.utility.moving_average (kimimaro/utility.py:647-664): the mean over the trailing window a[i-n+1 .. i] along axis 0 of
+    the input extended by n entries on both sides (np.pad's `mode`), accumulated in float64 as one running sum; the output has the
+    input's length.  n == 1 and an empty input come back as they are."""
+    if n <= 0:
+        raise ValueError("Window size (%s), must be >= 1." % (n,))
+    if n == 1 or len(a) == 0:
+        return a
+    width = [[n, n]] + [[0, 0]] * (a.ndim - 1)
+    running = np.cumsum(np.pad(a, width, mode=mode), dtype=np.float64, axis=0)
+    out = running[n:len(running) - n] - running[:len(running) - 2 * n]
+    out /= float(n)
+    return out
+
+
+def _add_property(skel, prop):
+    """utility.py:104-112"""
+    if not any(a["id"] == prop["id"] for a in skel.extra_attributes):
+        skel.extra_attributes.append(dict(prop))
+
+
+def _xs_check_arguments(step, smoothing_window, visualize_section_planes, fill_holes=False):
+    assert step > 0
+    assert smoothing_window > 0
+    if visualize_section_planes:
+        raise NotImplementedError("visualize_section_planes=True paints the planes for microviewer, which is not a dependency here")
+    if fill_holes:
+        raise NotImplementedError("cross_sectional_area(fill_holes=True): the reference fills every label's crop on its own; "
+                                  "per-label hole filling of a whole volume is not built (as for oversegment)")
+
+
+def _label_voxel_counts(eng, d_lab, words):
+    """how many voxels carry each of `words` (the unsigned words of the device labels) -> {word: count}"""
+    t = eng.torch
+    words = sorted(set(int(w) for w in words))
+    if not words:
+        return {}
+    bits = 8 * d_lab.element_size()
+    native = [w - (1 << bits) if d_lab.dtype.is_signed and w >= 1 << (bits - 1) else w for w in words]     # (u16 / u32 words in signed tensors)
+    order = np.argsort(native)
+    table = t.tensor([native[k] for k in order], dtype=d_lab.dtype, device=eng.device)
+    counts = t.zeros(len(words) + 1, dtype=t.int64, device=eng.device)
+    for chunk in d_lab.split(1 << 24):
+        at = t.searchsorted(table, chunk).clamp_(max=len(words) - 1)
+        at = t.where(table[at] == chunk, at, t.full_like(at, len(words)))
+        counts += t.bincount(at, minlength=len(words) + 1)
+    counts = counts.cpu().numpy()
+    return {words[k]: int(counts[j]) for j, k in enumerate(order)}
+
+
+def _xs_occurrences(skel, an, offset, shape, smoothing_window, step):
+    """The (vertex, normal) pairs the loop of utility.py:269-332 visits, in its order.  Returns (vox int64 (n, 3): every vertex's
+    voxel; occ_vertex int64 [m]; occ_normal f64 [m, 3])."""
+    v = np.asarray(skel.vertices).reshape(-1, 3)
+    if skel.space == "physical":
+        vox = (v / an).round().astype(np.int64)                        # utility.py:238-239
+    else:
+        vox = np.round(v).astype(np.int64)                             # (UNPINNED for vertices that are not integral)
+    vox = vox - np.asarray(offset, dtype=np.int64).reshape(1, 3)
+    n = vox.shape[0]
+    occ_vertex, occ_normal = [np.zeros(0, dtype=np.int64)], [np.zeros((0, 3), dtype=np.float64)]
+    if n:
+        # utility.py:246: `mapping` sends a voxel to the LAST vertex that lies in it
+        _, inverse = np.unique(vox, axis=0, return_inverse=True)
+        inverse = np.asarray(inverse).reshape(-1)
+        last = np.zeros(int(inverse.max()) + 1, dtype=np.int64)
+        np.maximum.at(last, inverse, np.arange(n))
+        canon = last[inverse]
+        extent = np.array(shape, dtype=np.int64)
+        for path in skel.paths(return_indices=True):
+            pts = vox[path]
+            normals = (pts[1:] - pts[:-1]).astype(np.float32)
+            normals = np.concatenate([normals, normals[-1:]])
+            normals = moving_average(normals, smoothing_window)                       # forwards, then backwards: no phase shift
+            normals = moving_average(normals[::-1], smoothing_window)[::-1]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                normals = normals / np.linalg.norm(normals, axis=1, keepdims=True)
+            i = np.arange(len(path))
+            keep = ((i + 1) % step == 0) | (i == 0) | (i == len(path) - 1)            # utility.py:285-294: both ends stay
+            keep &= np.all((pts >= 0) & (pts < extent), axis=1)
+            occ_vertex.append(canon[path[keep]])
+            occ_normal.append(normals[keep].astype(np.float64))
+    return vox, np.concatenate(occ_vertex), np.concatenate(occ_normal)
+
+
+def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats):
+    """jobs: (skeleton, the device word of its label, the offset of the volume in the skeleton's voxel frame).  The sequential loop
+    of the reference treats every vertex on its own -- a section depends on (voxel, normal, label) alone -- so its outcome is: a
+    branch point is evaluated at every occurrence and ends as the mean; any other vertex is evaluated at its first occurrence when
+    its area is 0 (or, repairing, its contact is not), then at the next one for as long as the area comes back 0.  Round 0 launches
+    the first group, every later round the vertices that came back 0 and occur again."""
+    t0 = time.perf_counter()
+    an64 = an.astype(np.float64)
+    starts, area_parts, contact_parts, seed_parts, word_parts, branch_parts, occ_v, occ_n = [0], [], [], [], [], [], [], []
+    for skel, word, offset in jobs:
+        nv = int(np.asarray(skel.vertices).reshape(-1, 3).shape[0])
+        if repair_contacts or (multipass and hasattr(skel, "cross_sectional_area")):       # utility.py:250-255
+            area_parts.append(np.array(skel.cross_sectional_area, dtype=np.float32).reshape(-1))
+            contact_parts.append(np.array(skel.cross_sectional_area_contacts, dtype=np.uint8).reshape(-1))
+            assert area_parts[-1].size == nv and contact_parts[-1].size == nv
+        else:
+            area_parts.append(np.zeros(nv, dtype=np.float32))
+            contact_parts.append(np.zeros(nv, dtype=np.uint8))
+        vox, ov, on = _xs_occurrences(skel, an, offset, shape, smoothing_window, step)
+        seed_parts.append(section.seed_index(vox, shape))
+        word_parts.append(np.full(nv, word, dtype=np.uint32))
+        is_branch = np.zeros(nv, dtype=bool)
+        is_branch[skel.branches()] = True
+        branch_parts.append(is_branch)
+        occ_v.append(ov + starts[-1])
+        occ_n.append(on)
+        starts.append(starts[-1] + nv)
+    cat = lambda parts, dtype: np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
+    areas, contacts = cat(area_parts, np.float32), cat(contact_parts, np.uint8)
+    seeds, words, branch = cat(seed_parts, np.uint32), cat(word_parts, np.uint32), cat(branch_parts, bool)
+    occ_v = cat(occ_v, np.int64)
+    occ_n = np.concatenate(occ_n) if occ_n else np.zeros((0, 3), dtype=np.float64)
+
+    t1 = t2 = time.perf_counter()
+    rounds = 0
+    sv = occ_v
+    if occ_v.size:
+        # the occurrences of every vertex side by side, in the loop's order
+        order = np.argsort(occ_v, kind="stable")
+        sv, sn = occ_v[order], occ_n[order]
+        first = np.ones(sv.size, dtype=bool)
+        first[1:] = sv[1:] != sv[:-1]
+        group_start = np.flatnonzero(first)
+        group_end = np.append(group_start[1:], sv.size)
+        last_of_vertex = np.zeros(sv.size, dtype=bool)
+        last_of_vertex[group_end - 1] = True
+
+        def launch(which):
+            return section.cross_sections(eng, d_lab, label_bytes, shape, an64, seeds[sv[which]], words[sv[which]], sn[which], stats)[:2]
+
+        t1 = time.perf_counter()
+        open0 = (areas[sv] == 0) | ((contacts[sv] > 0) if repair_contacts else False)
+        at_branch = branch[sv]
+        batch = np.flatnonzero(at_branch | (first & open0))
+        got_area, got_contact = launch(batch)
+        t2 = time.perf_counter()
+        # branch points: the mean of all their values (float32, summed in the loop's order), the contacts of all / of the last
+        is_b = at_branch[batch]
+        b_pos, b_area, b_contact = batch[is_b], got_area[is_b], got_contact[is_b]
+        if b_pos.size:
+            if repair_contacts:
+                ends = last_of_vertex[b_pos]
+                contacts[sv[b_pos[ends]]] = b_contact[ends]
+            else:
+                np.bitwise_or.at(contacts, sv[b_pos], b_contact)
+            cuts = np.flatnonzero(first[b_pos])
+            for lo, hi in zip(cuts, np.append(cuts[1:], b_pos.size)):
+                total = np.float32(0)
+                for value in b_area[lo:hi]:
+                    total = np.float32(total + value)
+                areas[sv[b_pos[lo]]] = np.float32(total / np.float32(hi - lo))
+        pending, p_area, p_contact = batch[~is_b], got_area[~is_b], got_contact[~is_b]
+        rounds = 1
+        while pending.size:
+            v = sv[pending]
+            areas[v] = p_area
+            contacts[v] = p_contact if repair_contacts else contacts[v] | p_contact
+            again = (p_area == 0) & ~last_of_vertex[pending]
+            pending = pending[again] + 1
+            if pending.size:
+                p_area, p_contact = launch(pending)
+                rounds += 1
+    t3 = time.perf_counter()
+    for k, (skel, _, _) in enumerate(jobs):
+        skel.cross_sectional_area = areas[starts[k]:starts[k + 1]].copy()
+        skel.cross_sectional_area_contacts = contacts[starts[k]:starts[k + 1]].copy()
+    if stats is not None:
+        stats["prepare_s"] = stats.get("prepare_s", 0.0) + (t1 - t0)
+        stats["first_launch_s"] = stats.get("first_launch_s", 0.0) + (t2 - t1)
+        stats["finish_s"] = stats.get("finish_s", 0.0) + (t3 - t2)
+        stats["rounds"] = rounds
+        stats["vertices"] = int(starts[-1])
+        stats["occurrences"] = int(sv.size)
+
+
+def _xs_anisotropy(anisotropy):
+    an = np.array(anisotropy, dtype=np.float32).reshape(-1)
+    if an.shape != (3,) or not np.all(np.isfinite(an)) or not np.all(an > 0):
+        raise ValueError("anisotropy must be three finite positive numbers")
+    return an
+
+
+def cross_sectional_area_single(binimg, skel, roi=None, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
+                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None):
+    """kimimaro.cross_sectional_area_single (kimimaro/utility.py:168-349): the cross sectional areas of ONE skeleton against a binary
+    image of its object (foreground = non-zero; numpy, or a torch tensor on the GPU).  roi: where the image sits in the skeleton's
+    voxel frame -- anything with a `.minpt`, or three numbers -- subtracted from the vertices.  Everything else as
+    cross_sectional_area.  The skeleton is changed in place and returned."""
+    _xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    from . import points
+    from .ops import engine
+    img = points.check_binary_image(binimg)
+    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    an = _xs_anisotropy(anisotropy)
+    d_img, shape = points.device_binary_image(eng, img)
+    offset = np.zeros(3, dtype=np.int64) if roi is None else np.asarray(getattr(roi, "minpt", roi), dtype=np.int64).reshape(3)
+    _xs_run(eng, d_img, 1, shape, an, [(skel, 1, offset)], smoothing_window, step, multipass, repair_contacts, _stats)
+    _add_property(skel, XS_PROP)
+    _add_property(skel, XS_CONTACT_PROP)
+    return skel
+
+
+def cross_sectional_area(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
+                         fill_holes=False, multipass=False, repair_contacts=False, visualize_section_planes=False, step=1,
+                         _stats=None):
+    """kimimaro.cross_sectional_area (kimimaro/utility.py:351-560): for every vertex of every skeleton the area of the section of its
+    label by the plane through the vertex's voxel whose normal points to the next vertex of the path (the part of
+    the plane inside the 26-connected piece of cut voxels of the label around the vertex).  Every skeleton gains
+
+      cross_sectional_area           float32 per vertex, physical units; -1 everywhere for a skeleton that was skipped
+      cross_sectional_area_contacts  uint8 per vertex: bits 1, 2 the section touches the x = 0 / x = sx-1 face of the volume,
+                                     4, 8 the y faces, 16, 32 the z faces -- the area may be an underestimate
+
+    and both entries in extra_attributes.  The skeletons are changed in place and returned (dict -> dict, list -> list, one -> one).
+
+    smoothing_window > 1 smooths the normals along every path (moving_average, forwards and backwards); step > 1 evaluates every
+    step-th vertex of a path and its two ends; multipass keeps existing values and re-evaluates vertices whose area is 0 (several
+    volumes, one skeleton); repair_contacts re-evaluates vertices whose contact is not 0 (after widening the volume).
+    A skeleton is skipped when its id is 0, its label does not occur or occupies a single voxel (utility.py:141-154); a bool volume
+    assigns every skeleton to label 1.  all_labels: numpy, or a torch tensor on the GPU indexed [x, y, z].
+    `progress` and `in_place` are accepted and have no effect."""
+    _xs_check_arguments(step, smoothing_window, visualize_section_planes, fill_holes)
+    from .ops import engine
+    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    an = _xs_anisotropy(anisotropy)
+    skels = _skeleton_list(skeletons)
+    d_flat, itemsize, is_bool, shape, _, span = _device_labels(eng, all_labels)
+    if shape[0] * shape[1] * shape[2] >= 2 ** 32 - 1:
+        raise ValueError("the volume must hold fewer than 2^32 - 1 voxels")
+    labels_of = [_label_of(s, is_bool) for s in skels]
+    d_lab, label_bytes, device_label = _narrow_labels(eng, d_flat, itemsize, span, {L for L in labels_of if L is not None})
+    counts = _label_voxel_counts(eng, d_lab, device_label.values())
+    jobs = [(s, device_label[L], (0, 0, 0)) for s, L in zip(skels, labels_of)
+            if L is not None and L in device_label and counts[device_label[L]] >= 2]       # utility.py:141-154
+    _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats)
+    for s in skels:                                                                        # utility.py:551-558
+        _add_property(s, XS_PROP)
+        _add_property(s, XS_CONTACT_PROP)
+        if not hasattr(s, "cross_sectional_area"):
+            s.cross_sectional_area = np.full(len(s.vertices), -1, dtype=np.float32)
+        if not hasattr(s, "cross_sectional_area_contacts"):
+            s.cross_sectional_area_contacts = np.zeros(len(s.vertices), dtype=np.uint8)
+    return skeletons
