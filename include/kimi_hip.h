@@ -403,6 +403,43 @@ int kh_fill_voids(const uint8_t* mask, int64_t sx, int64_t sy, int64_t sz, uint3
 int kh_fill_voids_nd(const uint8_t* mask, int ndim, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint8_t* open,
                      uint8_t* out, int64_t* filled, void* stream);
 
+/* ---- kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795): the holes of EVERY label in one pass over the volume
+ * (csrc/ccl.hip).  hole(L) = the union of the 6-connected components of {v : labels[v] != L} that own no voxel on a
+ * face of the array -- what fill_voids.fill paints on L's bounding box.  A REGION is a 6-connected component of equal value, 0
+ * included; hole(L) is a union of regions, so the volume is read for the regions, their table and their adjacency only.
+ * labels: u8/u16/u32/u64 [sx,sy,sz] (label_bytes 1, 2, 4 or 8), fewer than 2^32 - 1 voxels.
+ * kh_regions6: region (u32 [nvox]) = ids 1..R by first appearance in the raster, *nregions (device u32) = R, representative
+ *   (u32 [nvox + 1]): [r] = smallest linear index of region r; parent (u32 [nvox]), chunk_counts (u32 [ceil(nvox / 1024)]): scratch.
+ * kh_region_table: value (u64 [R + 1]) = the label a region carries, count (u32 [R + 1]) = its voxels, face (u8 [R + 1]) = 1 iff
+ *   it owns a voxel on a face of the array; entry 0 is 0.  ndim as in kh_fill_voids_nd: an axis beyond it (extent 1) has no faces;
+ *   an axis of extent 1 WITHIN ndim puts every voxel on a face.
+ * kh_region_pairs: table (u64 [capacity], capacity a power of two >= 64; set by the call) = an open-addressing hash set of the
+ *   unordered pairs of regions that share a voxel face, key = smaller id << 32 | larger id, 0 = empty slot, in no particular order;
+ *   state (device u32 [2], set by the call): [0] = keys in the table, [1] != 0: the table was too small and holds a PART of the
+ *   set -- call again with a larger one (memory is bounded by the capacity, not by the number of faces).
+ * kh_region_apply: labels[v] = owner[region[v]] where that is non-zero (owner: u64 [R + 1]), in place.                          */
+int kh_regions6(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint32_t* chunk_counts,
+                uint32_t* region, uint32_t* representative, uint32_t* nregions, void* stream);
+int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative, int64_t nregions,
+                    int ndim, int64_t sx, int64_t sy, int64_t sz, uint64_t* value, uint32_t* count, uint8_t* face, void* stream);
+int kh_region_pairs(const uint32_t* region, int64_t sx, int64_t sy, int64_t sz, uint64_t* table, int64_t capacity, uint32_t* state,
+                    void* stream);
+int kh_region_apply(const uint32_t* region, const uint64_t* owner, void* labels, int label_bytes, int64_t nvox, void* stream);
+/* host (no GPU needed): who fills what, on the region graph.  value / count / face: the table of kh_region_table ([nregions + 1]);
+ * pairs: u64 [npairs], the non-empty keys of kh_region_pairs in any order, each unordered pair once.  The labels (non-zero values,
+ * compared as unsigned words) are gone through in ascending order with a dead set, as the reference's loop does:
+ *   a label that is not dead and has hole(L) != {} adds |hole(L)| to *filled, kills every label with a region in hole(L) and
+ *   becomes the owner of hole(L)'s regions (a later owner replaces an earlier one; *filled counts such a voxel twice).
+ * hole(L) = the regions that no path of the graph joins to a face-owning region once L's regions are removed.
+ * owner (u64 [nregions + 1]) = the label a region ends up with, 0 = it keeps its own; label_value / label_state ([nregions],
+ * the first `return value` entries are set) = the distinct labels ascending and KH_HOLES_* bits for each.
+ * Returns the number of labels, -1 on allocation failure, -2 on bad arguments (null pointer, a pair outside 1..nregions).      */
+#define KH_HOLES_PROCESSED 1   /* the label was alive at its turn: its holes were looked for          */
+#define KH_HOLES_FILLED 2      /* ... and it had some                                               */
+#define KH_HOLES_KILLED 4      /* a region of the label lies in a hole that was filled (at any time) */
+int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value, const uint32_t* count, const uint8_t* face, int64_t npairs,
+                              const uint64_t* pairs, uint64_t* owner, uint64_t* label_value, uint8_t* label_state, int64_t* filled);
+
 /* ---- kimimaro.oversegment (kimimaro/utility.py:562-644) / dijkstra3d.euclidean_distance_field(..., return_feature_map=True) from
  * MANY sources: the geodesic Voronoi diagram of seed voxels inside every label, over the whole volume at once (csrc/feature.hip,
  * DESIGN.md 3.10).  PARITY UNPINNED (dijkstra3d and fastremap are absent from the reference tree); the result is defined order free:

@@ -23,6 +23,7 @@ SYMBOLS = [
     "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
     "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
     "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel",
+    "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes",
 ]
 
 
@@ -58,6 +59,7 @@ PDRF_KEEP_OTHERS = 0x100         # KH_PDRF_KEEP_OTHERS
 # flags of kh_trace_paths (KH_TRACE_*; tests/test_abi.py compares them with the header)
 TRACE_PROFILE, TRACE_HEAP_PRIO, TRACE_THREADS_64, TRACE_THREADS_128, TRACE_NO_GHOSTS, TRACE_GHOST_PARANOID = 1, 2, 4, 8, 16, 32
 TRACE_BIG_LDS_HEAP, TRACE_VOXEL_GRAPH, TRACE_SCRATCH_POOL, TRACE_FUSED_EDF = 64, 128, 256, 512
+HOLES_PROCESSED, HOLES_FILLED, HOLES_KILLED = 1, 2, 4    # KH_HOLES_*: the label states of kh_host_resolve_holes
 BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of kh_geodesic_relax / kh_feature_relax
 NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
 
@@ -163,10 +165,17 @@ def lib():
     L.kh_cross_sections_scratch_bytes.argtypes = [i64, i64, i64, i64]
     L.kh_cross_sections_scratch_bytes.restype = i64
     L.kh_host_section_voxel.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.kh_regions6.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.kh_region_table.argtypes = [vp, ci, vp, vp, i64, ci, i64, i64, i64, vp, vp, vp, vp]
+    L.kh_region_pairs.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp]
+    L.kh_region_apply.argtypes = [vp, vp, vp, ci, i64, vp]
+    L.kh_host_resolve_holes.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.kh_host_resolve_holes.restype = i64
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",
-                        "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths"):
+                        "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths",
+                        "kh_host_resolve_holes"):
             getattr(L, name).restype = ci
     _lib = L
     return L

@@ -473,3 +473,245 @@ extern "C" int kh_edt_graph_sample(const float* fine, int64_t sx, int64_t sy, in
   KH_LAUNCH_CHECK();
   return KH_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Holes of every label in one pass (kimimaro.intake.fill_all_holes, kimimaro/intake.py:747-795).
+// A REGION is a 6-connected component of equal value, value 0 included.  hole(L) -- what the reference's per-crop fill_voids.fill
+// paints with L -- is a union of regions, so the voxel work is one union-find over the volume (the one above, on the 3 already-
+// rastered face neighbours of equal value), a table per region, and the set of region pairs that share a voxel face; which region
+// goes to whom is decided on that small graph by the host (kh_host_resolve_holes, common.hip).
+namespace kh {
+
+// init: as ccl_init_kernel, but every voxel takes part (0 is a value like any other)
+template <typename LT>
+__global__ __launch_bounds__(256) void reg_init_kernel(const LT* __restrict__ lab, uint32_t* __restrict__ parent, int sx, int64_t nrows) {
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * nrows;
+  const int lane = threadIdx.x & 63;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int x = (int)(t % xt) * 256 + threadIdx.x;
+    const int64_t i = x + (int64_t)sx * (t / xt);
+    const LT L = x < sx ? lab[i] : (LT)0;
+    LT Lm = (LT)__shfl_up((unsigned long long)L, 1);
+    const bool start = lane == 0 || Lm != L;      // (the lanes behind the row's end come after its voxels: they start no run of theirs)
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(start) & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull));
+    if (x < sx) parent[i] = (uint32_t)(i - (lane - (63 - __clzll((long long)m))));
+  }
+}
+
+// link: the x runs are pre-linked inside every 64-lane chunk (one union where a run crosses a chunk boundary).  The voxel above /
+// in front is linked unless the voxel to the left has the value and so has ITS neighbour in that row: the two rows' runs then
+// overlap further left, and the leftmost voxel of the overlap has made the link.
+template <typename LT>
+__global__ __launch_bounds__(256) void reg_link_kernel(const LT* __restrict__ lab, uint32_t* parent, int sx, int sy, int sz) {
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * sy * sz;
+  const int64_t sxy = (int64_t)sx * sy;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int x = (int)(t % xt) * 256 + threadIdx.x;
+    const int64_t r = t / xt;
+    const int y = (int)(r % sy), z = (int)(r / sy);
+    if (x >= sx) continue;
+    const int64_t i = x + (int64_t)sx * y + sxy * z;
+    const LT L = lab[i];
+    const bool left = x > 0 && lab[i - 1] == L;
+    if (left && (x & 63) == 0) ccl_union(parent, (uint32_t)i, (uint32_t)(i - 1));
+    if (y > 0 && lab[i - sx] == L && !(left && lab[i - sx - 1] == L)) ccl_union(parent, (uint32_t)i, (uint32_t)(i - sx));
+    if (z > 0 && lab[i - sxy] == L && !(left && lab[i - sxy - 1] == L)) ccl_union(parent, (uint32_t)i, (uint32_t)(i - sxy));
+  }
+}
+
+template <typename LT>
+static int regions_impl(const LT* lab, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint32_t* chunk_counts, uint32_t* out,
+                        uint32_t* rep, uint32_t* total, hipStream_t st) {
+  const int64_t n = sx * sy * sz;
+  const int64_t nchunks = (n + 1023) / 1024;
+  const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
+  hipLaunchKernelGGL((reg_init_kernel<LT>), dim3(ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, lab, parent, (int)sx, sy * sz);
+  hipLaunchKernelGGL((reg_link_kernel<LT>), dim3(ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, lab, parent, (int)sx, (int)sy, (int)sz);
+  hipLaunchKernelGGL(ccl_flatten_count_kernel, dim3(ccl_grid(nchunks, 1)), dim3(256), 0, st, parent, n, chunk_counts);
+  hipLaunchKernelGGL(ccl_scan_kernel, dim3(1), dim3(1024), 0, st, chunk_counts, nchunks, total);
+  hipLaunchKernelGGL(ccl_number_roots_kernel, dim3(ccl_grid(nchunks, 1)), dim3(256), 0, st, parent, n, chunk_counts, out, rep);
+  hipLaunchKernelGGL(ccl_relabel_kernel, dim3(ccl_grid(n, 256)), dim3(256), 0, st, parent, n, out, (uint16_t*)nullptr, total);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+// table, per region: the value (read at its representative voxel), the voxel count, whether it owns a voxel on a face of the array.
+template <typename LT>
+__global__ __launch_bounds__(256) void reg_value_kernel(const LT* __restrict__ lab, const uint32_t* __restrict__ rep, int64_t nregions,
+                                                        unsigned long long* __restrict__ value) {
+  for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r <= nregions; r += (int64_t)gridDim.x * 256)
+    value[r] = r == 0 ? 0ull : (unsigned long long)lab[rep[r]];
+}
+
+// lanes along x: the first lane of a run of equal region ids inside its 64-lane chunk adds the run's length and sets the face flag
+// for the whole run (one atomic per run, not per voxel; the flag is looked at before it is written)
+__global__ __launch_bounds__(256) void reg_table_kernel(const uint32_t* __restrict__ region, int sx, int sy, int sz, int ndim,
+                                                        uint32_t* __restrict__ count, uint8_t* face) {
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * sy * sz;
+  const int lane = threadIdx.x & 63;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int x = (int)(t % xt) * 256 + threadIdx.x;
+    const int64_t row = t / xt;
+    const int y = (int)(row % sy), z = (int)(row / sy);
+    const bool valid = x < sx;
+    const uint32_t r = valid ? region[x + (int64_t)sx * row] : 0u;      // (0 is no region id)
+    const uint32_t rm = __shfl_up(r, 1);
+    const bool start = valid && (lane == 0 || rm != r);
+    const unsigned long long starts = __builtin_amdgcn_ballot_w64(start);
+    const int nvalid = __popcll(__builtin_amdgcn_ballot_w64(valid));   // the valid lanes of a chunk are its first ones
+    if (start) {
+      const unsigned long long later = lane == 63 ? 0ull : (starts & ~((2ull << lane) - 1ull));
+      const int end = later ? __builtin_ctzll(later) : nvalid;
+      const int len = end - lane;
+      atomicAdd(&count[r], (uint32_t)len);
+      const bool f = x == 0 || x + len == sx || (ndim >= 2 && (y == 0 || y == sy - 1)) || (ndim >= 3 && (z == 0 || z == sz - 1));
+      if (f && face[r] == 0) face[r] = 1;
+    }
+  }
+}
+
+// pairs: the set of unordered pairs of regions that share a voxel face, as keys (smaller id << 32 | larger id) in an open-addressing
+// hash set in HBM (0 = empty slot; linear probing).  A key equal to the previous lane's key of the same direction is dropped first
+// (a run of one region lying on a run of another gives one key per 64 lanes); the slot is read with a plain load before any
+// compare-and-swap, so a pair that is in the set already costs no atomic.  A probe sequence longer than REG_MAX_PROBES sets
+// state[1]: the caller retries with a larger table.  state[0] counts the keys inserted.
+static constexpr int REG_MAX_PROBES = 512;
+__device__ __forceinline__ void reg_pair_insert(unsigned long long* table, unsigned long long mask, unsigned long long key, uint32_t* state) {
+  unsigned long long h = key * 0x9E3779B97F4A7C15ull;
+  h ^= h >> 29;
+  h *= 0xBF58476D1CE4E5B9ull;
+  h ^= h >> 32;
+  unsigned long long slot = h & mask;
+  for (int probe = 0; probe < REG_MAX_PROBES; probe++, slot = (slot + 1) & mask) {
+    const unsigned long long cur = __hip_atomic_load(&table[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) return;
+    if (cur != 0ull) continue;
+    const unsigned long long old = atomicCAS(&table[slot], 0ull, key);
+    if (old == 0ull) { atomicAdd(&state[0], 1u); return; }
+    if (old == key) return;
+  }
+  __hip_atomic_store(&state[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void reg_pairs_kernel(const uint32_t* __restrict__ region, int sx, int sy, int sz,
+                                                        unsigned long long* table, unsigned long long mask, uint32_t* state) {
+  const int xt = (sx + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * sy * sz;
+  const int64_t sxy = (int64_t)sx * sy;
+  const int lane = threadIdx.x & 63;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    // a table that has overflowed is abandoned (the whole wave leaves: the shuffles below need all of its lanes)
+    if (__shfl(__hip_atomic_load(&state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0) != 0u) return;
+    const int x = (int)(t % xt) * 256 + threadIdx.x;
+    const int64_t row = t / xt;
+    const int y = (int)(row % sy), z = (int)(row / sy);
+    const bool valid = x < sx;
+    const int64_t i = x + (int64_t)sx * row;
+    const uint32_t r = valid ? region[i] : 0u;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      const bool there = valid && (d == 0 ? x > 0 : (d == 1 ? y > 0 : z > 0));
+      const uint32_t q = there ? region[i - (d == 0 ? 1 : (d == 1 ? (int64_t)sx : sxy))] : r;
+      unsigned long long key = q == r ? 0ull : (((unsigned long long)(q < r ? q : r) << 32) | (unsigned long long)(q < r ? r : q));
+      const unsigned long long before = __shfl_up(key, 1);
+      if (lane > 0 && before == key) key = 0ull;
+      if (key != 0ull) reg_pair_insert(table, mask, key, state);
+    }
+  }
+}
+
+// apply: a voxel of a region with an owner takes the owner's value
+template <typename LT>
+__global__ __launch_bounds__(256) void reg_apply_kernel(const uint32_t* __restrict__ region, const unsigned long long* __restrict__ owner,
+                                                        LT* __restrict__ lab, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const unsigned long long o = owner[region[i]];
+    if (o != 0ull) lab[i] = (LT)o;
+  }
+}
+
+}  // namespace kh
+
+#define KH_REG_DISPATCH(bytes, name, CALL)                   \
+  switch (bytes) {                                           \
+    case 1: { typedef uint8_t LT; CALL; } break;             \
+    case 2: { typedef uint16_t LT; CALL; } break;            \
+    case 4: { typedef uint32_t LT; CALL; } break;            \
+    case 8: { typedef uint64_t LT; CALL; } break;            \
+    default: kh::set_error(name ": label_bytes must be 1, 2, 4 or 8"); return KH_EINVAL; \
+  }
+
+extern "C" int kh_regions6(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent,
+                           uint32_t* chunk_counts, uint32_t* region, uint32_t* representative, uint32_t* nregions, void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!labels || !parent || !chunk_counts || !region || !representative || !nregions || sx <= 0 || sy <= 0 || sz <= 0 ||
+      sx >= (1ll << 31) || sy >= (1ll << 31) || sz >= (1ll << 31) || sx * sy * sz >= (1ll << 32) - 1) {
+    kh::set_error("kh_regions6: bad arguments (null pointer, empty volume or >= 2^32-1 voxels)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_REG_DISPATCH(label_bytes, "kh_regions6",
+                  return kh::regions_impl((const LT*)labels, sx, sy, sz, parent, chunk_counts, region, representative, nregions, st));
+  return KH_OK;
+}
+
+extern "C" int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative,
+                               int64_t nregions, int ndim, int64_t sx, int64_t sy, int64_t sz, uint64_t* value, uint32_t* count,
+                               uint8_t* face, void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!labels || !region || !representative || !value || !count || !face || sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) ||
+      sy >= (1ll << 31) || sz >= (1ll << 31) || sx * sy * sz >= (1ll << 32) - 1 || nregions < 1 || nregions > sx * sy * sz ||
+      ndim < 1 || ndim > 3 || (ndim < 3 && sz != 1) || (ndim < 2 && sy != 1)) {
+    kh::set_error("kh_region_table: bad arguments (null pointer, empty volume, >= 2^32-1 voxels, nregions outside [1, nvox], or an "
+                  "axis beyond ndim with extent > 1)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(uint32_t) * (size_t)(nregions + 1), st));
+  KH_HIP_CHECK(hipMemsetAsync(face, 0, (size_t)(nregions + 1), st));
+  KH_REG_DISPATCH(label_bytes, "kh_region_table",
+                  hipLaunchKernelGGL((kh::reg_value_kernel<LT>), dim3(kh::ccl_grid(nregions + 1, 256)), dim3(256), 0, st,
+                                     (const LT*)labels, representative, nregions, (unsigned long long*)value));
+  const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
+  hipLaunchKernelGGL(kh::reg_table_kernel, dim3(kh::ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, region, (int)sx, (int)sy, (int)sz,
+                     ndim, count, face);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_region_pairs(const uint32_t* region, int64_t sx, int64_t sy, int64_t sz, uint64_t* table, int64_t capacity,
+                               uint32_t* state, void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!region || !table || !state || sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) || sy >= (1ll << 31) || sz >= (1ll << 31) ||
+      sx * sy * sz >= (1ll << 32) - 1 || capacity < 64 || (capacity & (capacity - 1)) != 0) {
+    kh::set_error("kh_region_pairs: bad arguments (null pointer, empty volume, >= 2^32-1 voxels, or a capacity that is no power of "
+                  "two >= 64)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_HIP_CHECK(hipMemsetAsync(table, 0, sizeof(uint64_t) * (size_t)capacity, st));
+  KH_HIP_CHECK(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), st));
+  const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
+  hipLaunchKernelGGL(kh::reg_pairs_kernel, dim3(kh::ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, region, (int)sx, (int)sy, (int)sz,
+                     (unsigned long long*)table, (unsigned long long)(capacity - 1), state);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_region_apply(const uint32_t* region, const uint64_t* owner, void* labels, int label_bytes, int64_t nvox,
+                               void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!region || !owner || !labels || nvox <= 0 || nvox >= (1ll << 32) - 1) {
+    kh::set_error("kh_region_apply: bad arguments (null pointer, empty volume or >= 2^32-1 voxels)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_REG_DISPATCH(label_bytes, "kh_region_apply",
+                  hipLaunchKernelGGL((kh::reg_apply_kernel<LT>), dim3(kh::ccl_grid(nvox, 256)), dim3(256), 0, st, region,
+                                     (const unsigned long long*)owner, (LT*)labels, nvox));
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}

@@ -446,3 +446,106 @@ extern "C" int64_t kh_host_find_border_targets(const float* dt, const uint32_t* 
   free(st);
   return norder;
 }
+
+// ---- kimimaro.intake.fill_all_holes (kimimaro/intake.py:763-790) on the region adjacency graph (see kimi_hip.h)
+extern "C" int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value, const uint32_t* count, const uint8_t* face,
+                                         int64_t npairs, const uint64_t* pairs, uint64_t* owner, uint64_t* label_value,
+                                         uint8_t* label_state, int64_t* filled) {
+  if (nregions < 0 || npairs < 0 || !value || !count || !face || (npairs && !pairs) || !owner || !label_value || !label_state || !filled)
+    return -2;
+  try {
+    const size_t R = (size_t)nregions;
+    std::vector<uint32_t> start(R + 2, 0u), adj((size_t)(2 * npairs));
+    for (int64_t p = 0; p < npairs; p++) {
+      const uint64_t a = pairs[p] >> 32, b = pairs[p] & 0xFFFFFFFFull;
+      if (a < 1 || b < 1 || a > (uint64_t)nregions || b > (uint64_t)nregions || a == b) return -2;
+      start[a + 1]++;
+      start[b + 1]++;
+    }
+    for (size_t r = 1; r <= R + 1; r++) start[r] += start[r - 1];        // the neighbours of r: adj[start[r] .. start[r + 1])
+    {
+      std::vector<uint32_t> at(start.begin(), start.end() - 1);
+      for (int64_t p = 0; p < npairs; p++) {
+        const uint32_t a = (uint32_t)(pairs[p] >> 32), b = (uint32_t)pairs[p];
+        adj[at[a]++] = b;
+        adj[at[b]++] = a;
+      }
+    }
+    // the regions of every non-zero value, values ascending
+    std::vector<uint32_t> order;
+    order.reserve(R);
+    for (size_t r = 1; r <= R; r++) {
+      owner[r] = 0;
+      if (value[r] != 0) order.push_back((uint32_t)r);
+    }
+    owner[0] = 0;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return value[a] != value[b] ? value[a] < value[b] : a < b; });
+    std::vector<int64_t> label_of(R + 1, -1);
+    std::vector<size_t> first;                                           // label k: order[first[k] .. first[k + 1])
+    for (size_t i = 0; i < order.size(); i++) {
+      if (i == 0 || value[order[i]] != value[order[i - 1]]) {
+        label_value[first.size()] = value[order[i]];
+        label_state[first.size()] = 0;
+        first.push_back(i);
+      }
+      label_of[order[i]] = (int64_t)first.size() - 1;
+    }
+    const int64_t nlabels = (int64_t)first.size();
+    first.push_back(order.size());
+
+    // seen[r] == epoch: r is a wall (a region of the label at hand) or was reached by a search of this label; open[r] == epoch: it
+    // reaches a face-owning region without crossing a wall.  A search ends at the first face-owning or open region it meets --
+    // everything it has seen so far is open then, and what it has not seen finds that out from there.
+    std::vector<uint32_t> seen(R + 1, 0u), open(R + 1, 0u), queue, holes;
+    uint32_t epoch = 0;
+    int64_t total = 0;
+    for (int64_t k = 0; k < nlabels; k++) {
+      if (label_state[k] & KH_HOLES_KILLED) continue;
+      label_state[k] |= KH_HOLES_PROCESSED;
+      if (++epoch == 0) {                                                // (2^32 labels: start the stamps over)
+        std::fill(seen.begin(), seen.end(), 0u);
+        std::fill(open.begin(), open.end(), 0u);
+        epoch = 1;
+      }
+      for (size_t i = first[(size_t)k]; i < first[(size_t)k + 1]; i++) seen[order[i]] = epoch;
+      holes.clear();
+      for (size_t i = first[(size_t)k]; i < first[(size_t)k + 1]; i++) {
+        const uint32_t wall = order[i];
+        for (uint32_t e = start[wall]; e < start[wall + 1]; e++) {
+          const uint32_t s = adj[e];
+          if (seen[s] == epoch) continue;
+          queue.clear();
+          queue.push_back(s);
+          seen[s] = epoch;
+          bool is_open = face[s] != 0;
+          for (size_t head = 0; head < queue.size() && !is_open; head++) {
+            const uint32_t u = queue[head];
+            for (uint32_t f = start[u]; f < start[u + 1]; f++) {
+              const uint32_t v = adj[f];
+              if (seen[v] == epoch) {
+                if (open[v] == epoch) { is_open = true; break; }
+                continue;
+              }
+              seen[v] = epoch;
+              queue.push_back(v);
+              if (face[v] != 0) { is_open = true; break; }
+            }
+          }
+          if (is_open) for (uint32_t u : queue) open[u] = epoch;
+          else holes.insert(holes.end(), queue.begin(), queue.end());
+        }
+      }
+      if (holes.empty()) continue;
+      label_state[k] |= KH_HOLES_FILLED;
+      for (uint32_t h : holes) {
+        total += (int64_t)count[h];
+        owner[h] = label_value[k];
+        if (label_of[h] >= 0) label_state[label_of[h]] |= KH_HOLES_KILLED;
+      }
+    }
+    *filled = total;
+    return nlabels;
+  } catch (const std::bad_alloc&) {
+    return -1;
+  }
+}

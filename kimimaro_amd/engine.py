@@ -99,6 +99,7 @@ class Engine:
         self.sweep_lds_levels = min(int(os.environ.get("KH_SWEEP_LDS_LEVELS", 8192)), _abi.SWEEP_LDS_LEVELS)
         self._level_tables = {}
         self.scratch_divisor = 1            # tests: shrink the heap / path scratch to exercise the overflow retry
+        self.holes_table_capacity = None    # tests: first size of fill_all_holes' pair table (a power of two), to exercise its retry
         self.arena_divisor = 1              # tests: shrink the sweep's event arena (a call that runs out falls back to the heap)
         # Cap of the level window (words of LDS per label's workgroup; an event beyond it abandons the call to the heap emulation).
         # The launch gives EVERY workgroup the LDS of its neediest label: at c3 one label of 3 402 wants 4 096 words (20 KB), which
@@ -261,6 +262,106 @@ class Engine:
         _abi.check(self.lib.kh_fill_voids_nd(self.ptr(d_mask), int(ndim), shape[0], shape[1], shape[2], self.ptr(d_parent),
                                              self.ptr(d_open), self.ptr(d_out), self.ptr(d_cnt), self.stream()))
         return d_out, int(d_cnt.cpu().numpy()[0])
+
+    def region_graph(self, d_lab, label_bytes, shape, ndim=3, mark=lambda name: None):
+        """The regions of a label volume resident in HBM (6-connected components of equal value, 0 included) and their adjacency:
+        kh_regions6 -> kh_region_table -> kh_region_pairs.  Returns (d_region: u32 ids 1..R per voxel on the device; value u64,
+        count u32, face u8: host arrays [R + 1]; pairs: host u64, every unordered pair of regions that share a voxel face once, as
+        smaller id << 32 | larger id, in no particular order; info: regions, pairs, table_capacity, table_tries, compact_ms).
+        mark(name) is called in front of and behind the launches of each pass (Engine.fill_all_holes puts HIP events there)."""
+        import time
+        t = self.torch
+        sx, sy, sz = shape
+        n = sx * sy * sz
+        mark("regions")
+        d_parent = self.empty(n, t.int32)
+        d_chunks = self.empty((n + 1023) // 1024, t.int32)
+        d_region = self.empty(n, t.int32)
+        d_rep = self.empty(n + 1, t.int32)
+        d_total = self.empty(1, t.int32)
+        _abi.check(self.lib.kh_regions6(self.ptr(d_lab), int(label_bytes), sx, sy, sz, self.ptr(d_parent), self.ptr(d_chunks),
+                                        self.ptr(d_region), self.ptr(d_rep), self.ptr(d_total), self.stream()))
+        mark("regions")
+        nreg = int(d_total.cpu().numpy().view(np.uint32)[0])
+        del d_parent, d_chunks
+        mark("table")
+        d_value = self.empty(nreg + 1, t.int64)
+        d_count = self.empty(nreg + 1, t.int32)
+        d_face = self.empty(nreg + 1, t.uint8)
+        _abi.check(self.lib.kh_region_table(self.ptr(d_lab), int(label_bytes), self.ptr(d_region), self.ptr(d_rep), nreg, int(ndim),
+                                            sx, sy, sz, self.ptr(d_value), self.ptr(d_count), self.ptr(d_face), self.stream()))
+        mark("table")
+        del d_rep
+        # the hash set of region pairs: 32 slots per region to begin with (a region of dense neuropil touches about a dozen others),
+        # never more than the 3 n faces can ask for; a table that overflows is reported by the kernel and tried again, 4 x larger
+        pow2 = lambda v: 1 << max(int(v) - 1, 1).bit_length()
+        limit = max(pow2(8 * n), 1 << 12)
+        cap = self.holes_table_capacity or min(max(pow2(32 * nreg), 1 << 12), limit)
+        tries = 0
+        while True:
+            tries += 1
+            d_table = self.empty(cap, t.int64)
+            d_state = self.empty(2, t.int32)
+            mark("pairs")
+            _abi.check(self.lib.kh_region_pairs(self.ptr(d_region), sx, sy, sz, self.ptr(d_table), cap, self.ptr(d_state), self.stream()))
+            mark("pairs")
+            state = d_state.cpu().numpy().view(np.uint32)
+            if state[1] == 0:
+                break
+            if cap >= limit:
+                raise _abi.KimiHipError("kh_region_pairs: the pair table overflows at %d slots for %d voxels" % (cap, n))
+            del d_table
+            cap *= 4
+        t0 = time.perf_counter()
+        pairs = d_table[d_table != 0].cpu().numpy().view(np.uint64)
+        del d_table
+        value = d_value.cpu().numpy().view(np.uint64)
+        count = d_count.cpu().numpy().view(np.uint32)
+        face = d_face.cpu().numpy()
+        if pairs.size != int(state[0]):
+            raise _abi.KimiHipError("kh_region_pairs: %d keys counted, %d found in the table" % (int(state[0]), pairs.size))
+        info = dict(regions=nreg, pairs=int(pairs.size), table_capacity=cap, table_tries=tries, compact_ms=(time.perf_counter() - t0) * 1e3)
+        return d_region, value, count, face, pairs, info
+
+    def fill_all_holes(self, d_lab, label_bytes, shape, ndim=3, stats=None):
+        """kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795) on a label volume resident in HBM (1-D, Fortran order, 1 / 2 / 4 /
+        8 bytes per label; modified in place): the holes of every label in ONE pass over the volume instead of a fill per bounding
+        box.  The regions, their table and their adjacency are made on the device (region_graph); the table and
+        the pairs (the only device-to-host traffic) go to kh_host_resolve_holes, which says who fills what; kh_region_apply paints.
+        ndim: dimensionality of the caller's array (kh_fill_voids_nd's meaning).  Returns the number of voxels filled.
+        stats (a dict, optional): region_graph's info, labels, label_value / label_state (the host's verdict per label,
+        _abi.HOLES_* bits), filled, resolve_ms, and -- at the price of a synchronisation at the end -- the HIP-event time of every
+        pass (regions_ms, table_ms, pairs_ms, apply_ms)."""
+        import time
+        from .intake import resolve_holes
+        self._narrow = None     # the volume is edited in place below: a u16 copy of it no longer matches
+        t = self.torch
+        shape = tuple(int(v) for v in shape) + (1,) * (3 - len(shape))
+        n = shape[0] * shape[1] * shape[2]
+        marks = []
+
+        def mark(name):
+            if stats is not None:
+                ev = t.cuda.Event(enable_timing=True)
+                ev.record(t.cuda.current_stream(self.device))
+                marks.append((name, ev))
+
+        d_region, value, count, face, pairs, info = self.region_graph(d_lab, label_bytes, shape, ndim, mark)
+        t0 = time.perf_counter()
+        owner, label_value, label_state, filled = resolve_holes(value, count, face, pairs)
+        t1 = time.perf_counter()
+        mark("apply")
+        if filled:
+            d_owner = t.from_numpy(owner.view(np.int64)).to(self.device)
+            _abi.check(self.lib.kh_region_apply(self.ptr(d_region), self.ptr(d_owner), self.ptr(d_lab), int(label_bytes), n, self.stream()))
+        mark("apply")
+        if stats is not None:
+            stats.update(info, labels=int(label_value.size), label_value=label_value, label_state=label_state, filled=int(filled),
+                         resolve_ms=(t1 - t0) * 1e3)
+            self.sync_stream()
+            for (name, a), (_, b) in zip(marks[0::2], marks[1::2]):
+                stats[name + "_ms"] = stats.get(name + "_ms", 0.0) + a.elapsed_time(b)
+        return int(filled)
 
     def to_host_volume(self, d, shape, dtype=np.uint32):
         return d.cpu().numpy().view(dtype).reshape(shape, order="F")

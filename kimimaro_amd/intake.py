@@ -184,7 +184,9 @@ def skeletonize(all_labels, teasar_params=DEFAULT_TEASAR_PARAMS, anisotropy=(1, 
         d_graph = eng.to_device(np.asfortranarray(vg.astype(np.uint32)))
     d_cc, nlabels, remapping = compute_cc_labels_device(eng, all_labels, d_graph)  # row f1 on the GPU
     if fill_holes:
-        fill_all_holes_device(eng, d_cc, all_labels.shape, nlabels)              # intake.py:168-169
+        # intake.py:168-169.  The per-label loop until the one-pass route (Engine.fill_all_holes, same result: tests/
+        # test_gpu_fill_holes.py) has been timed against it on c3 (tools/fill_holes_time.py; DESIGN.md 3.13, BENCH_NOTES.md)
+        fill_all_holes_device(eng, d_cc, all_labels.shape, nlabels)
     avocado = None
     if fix_avocados:
         # kimimaro/intake.py:187-193 run BEFORE everything else that looks at the components: it edits them (and renumbers them)
@@ -459,6 +461,74 @@ def fill_all_holes_device(eng, d_cc, shape, nlabels):
                 in_set[int(other)] = False
         sub[fb] = label
     return filled_total
+
+
+def resolve_holes(value, count, face, pairs):
+    """kh_host_resolve_holes (host C, no GPU needed): the reference's loop over the labels (kimimaro/intake.py:763-790) on the region
+    adjacency graph.  value (u64), count (u32), face (u8): the table of kh_region_table, [R + 1] with entry 0 unused; pairs (u64):
+    every unordered pair of regions that share a voxel face once, as smaller id << 32 | larger id.
+    Returns (owner u64 [R + 1]: the label a region is painted with, 0 = none; label_value u64 [nlabels]: the distinct non-zero
+    labels ascending; label_state u8 [nlabels]: _abi.HOLES_PROCESSED | HOLES_FILLED | HOLES_KILLED; number of voxels filled)."""
+    import ctypes as C
+    lib = _abi.lib()
+    value = np.ascontiguousarray(value, dtype=np.uint64)
+    count = np.ascontiguousarray(count, dtype=np.uint32)
+    face = np.ascontiguousarray(face, dtype=np.uint8)
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
+    if not (value.ndim == count.ndim == face.ndim == pairs.ndim == 1 and value.size == count.size == face.size >= 1):
+        raise ValueError("value, count and face are 1-D arrays of one length (regions + 1), pairs is 1-D")
+    nreg = value.size - 1
+    owner = np.zeros(nreg + 1, dtype=np.uint64)
+    label_value = np.zeros(max(nreg, 1), dtype=np.uint64)
+    label_state = np.zeros(max(nreg, 1), dtype=np.uint8)
+    filled = C.c_int64(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    nlab = lib.kh_host_resolve_holes(nreg, p(value), p(count), p(face), pairs.size, p(pairs), p(owner), p(label_value), p(label_state),
+                                     C.byref(filled))
+    if nlab == -1:
+        raise MemoryError("kh_host_resolve_holes failed")
+    if nlab < 0:
+        raise ValueError("kh_host_resolve_holes: a pair names a region outside 1..%d, or joins a region with itself" % nreg)
+    return owner, label_value[:nlab], label_state[:nlab], int(filled.value)
+
+
+def fill_all_holes(cc_labels, progress=False, return_fill_count=False):
+    """kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795): fills the holes of every label and removes the labels that get
+    filled in.  A hole of L is what fill_voids.fill paints on L's bounding box: the voxels that no 6-connected path outside L joins
+    to a face of the array.  The labels take their turn in ascending order; a label that lay (even partly) in a hole that was
+    filled does not get its own turn.
+
+    cc_labels: numpy array (any memory order, at most three non-trivial axes, integers or bool), or a torch tensor on the GPU
+      indexed [x, y(, z)].  It is modified in place and returned.  Values need not be dense, nor need a value be connected
+      (the reference asks for values below the number of voxels because it indexes find_objects' list); they are ordered as
+      the unsigned words the array holds.
+    progress: accepted, no effect.
+    return_fill_count: return (cc_labels, N), N = the number of voxels filled (a voxel filled twice counts twice, as there).
+
+    One pass over the volume on the MI355X (Engine.fill_all_holes); HipUnavailableError without one."""
+    from .ops import engine
+    from .utility import _device_labels
+    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    t = eng.torch
+    is_tensor = isinstance(cc_labels, t.Tensor)
+    if not is_tensor and not isinstance(cc_labels, np.ndarray):
+        raise TypeError("cc_labels must be a numpy array or a torch tensor (it is modified in place)")
+    if cc_labels.ndim < 1:
+        raise DimensionError("fill_all_holes needs an array with at least one axis")
+    filled = 0
+    if (cc_labels.numel() if is_tensor else cc_labels.size) > 0:
+        d_flat, itemsize, _, shape, shape0, _ = _device_labels(eng, cc_labels)
+        filled = eng.fill_all_holes(d_flat, itemsize, shape, ndim=min(cc_labels.ndim, 3))
+        if filled:
+            if is_tensor:
+                if d_flat.data_ptr() != cc_labels.data_ptr():          # (a Fortran-ordered view was edited where it lies)
+                    like = cc_labels.dtype if cc_labels.dtype == t.bool else d_flat.dtype
+                    cc_labels.view(like).copy_(d_flat.view(like).view(shape[2], shape[1], shape[0]).permute(2, 1, 0).reshape(shape0))
+            else:
+                word = np.dtype("u%d" % itemsize)
+                host = d_flat.cpu().numpy().view(word).reshape(shape, order="F")
+                cc_labels[...] = host.view(np.bool_ if cc_labels.dtype == np.bool_ else cc_labels.dtype).reshape(cc_labels.shape, order="F")
+    return (cc_labels, filled) if return_fill_count else cc_labels
 
 
 def shard_components(cc_segids, counts, rank, world):
