@@ -241,13 +241,10 @@ def test_pow2_exponent_mirrors_the_reference_test():
 def _key_table(an, rmax):
     """the flood's keys of all offsets up to rmax, with its float operation order (dijkstra_invalidation.hpp:310-316), and their
     ranks -- what Engine.level_table gets from kh_level_keys + torch.unique"""
+    from prep_ref import level_keys      # the one statement of the key's arithmetic; tests/test_gpu_prep.py holds kh_level_keys to it
     w = [np.float32(a) for a in an]
     dims = [int(rmax / float(w[i])) + 2 for i in range(3)]
-    a = (np.arange(dims[0], dtype=np.float32) * w[0]) ** 2
-    b = (np.arange(dims[1], dtype=np.float32) * w[1]) ** 2
-    c = (np.arange(dims[2], dtype=np.float32) * w[2]) ** 2
-    s = ((a[:, None, None] + b[None, :, None]).astype(np.float32) + c[None, None, :]).astype(np.float32)
-    keys3 = np.sqrt(s).astype(np.float32)
+    keys3 = level_keys(dims, w)
     uniq, inv = np.unique(keys3, return_inverse=True)
     return uniq, inv.reshape(keys3.shape), dims
 
