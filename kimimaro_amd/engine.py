@@ -31,7 +31,7 @@ def _torch():
 
 # the launch plan is pure numpy and lives in kimimaro_amd.plan; its names stay importable from here
 from .plan import (SCHED_LEVELS, SCRATCH_BYTES_PER_LABEL, SCRATCH_BYTES_PER_VOXEL, SCRATCH_POOL_FRACTION, SWEEP_FIELDS,  # noqa: F401
-                   LabelSet, arena_units, int_key_mode, int_levels, label_order, level_windows, plan_arena, plan_launches,
+                   LabelSet, LabelStats, arena_units, int_key_mode, int_levels, label_order, level_windows, plan_arena, plan_launches,
                    plan_spill, plan_sweep, plan_tasks, sweep_radii)
 
 
@@ -235,19 +235,23 @@ class Engine:
                                          self.ptr(d_counts), self.ptr(d_cc), self.ptr(d_rep), self.ptr(d_total), self.ptr(d_cc16),
                                          self.stream()))
         ncomp = int(d_total.cpu().numpy().view(np.uint32)[0])
-        # fewer than 65536 components: the u16 copy of the ids serves every later sweep (narrow())
-        # (keyed by the tensor OBJECT, which the record keeps alive: the caching allocator hands a freed volume's address
-        # to the next volume of the same size, so an address is no identity)
-        self._narrow = (d_cc, d_cc16) if ncomp < 65536 else None
+        if ncomp < 65536:
+            d_cc.kh_u16 = d_cc16      # the u16 copy of the ids serves every later sweep (narrow()); it lives as long as this object
         rep = d_rep[: ncomp + 1].cpu().numpy().view(np.uint32)
         return d_cc, ncomp, rep
 
     def narrow(self, d_cc):
-        """(device label volume, bytes per label) to sweep over: the u16 copy kh_ccl26 made of `d_cc` when there is one."""
-        nr = getattr(self, "_narrow", None)
-        if nr is not None and nr[0] is d_cc and d_cc is not None:
-            return nr[1], 2
-        return d_cc, 4
+        """(device label volume, bytes per label) to sweep over: the u16 copy kh_ccl26 made of `d_cc` when it carries one, else
+        (d_cc, 4).  The copy is an attribute of the tensor OBJECT ccl_device returned: a clone, a view or a converted tensor has
+        none.  The rule: whoever writes into the storage of such a tensor calls edited() on it first."""
+        d16 = getattr(d_cc, "kh_u16", None)
+        return (d_cc, 4) if d16 is None else (d16, 2)
+
+    @staticmethod
+    def edited(d):
+        """`d` is about to be written in place: the u16 copy it may carry (narrow()) no longer matches and is dropped."""
+        if hasattr(d, "kh_u16"):
+            del d.kh_u16
 
     def fill_voids(self, d_mask, shape, ndim=3):
         """kh_fill_voids (fill_voids.fill, kimimaro/trace.py:109) on a u8 mask resident in HBM; ndim < 3: a 2-D / 1-D image given as
@@ -334,7 +338,7 @@ class Engine:
         pass (regions_ms, table_ms, pairs_ms, apply_ms)."""
         import time
         from .intake import resolve_holes
-        self._narrow = None     # the volume is edited in place below: a u16 copy of it no longer matches
+        self.edited(d_lab)
         t = self.torch
         shape = tuple(int(v) for v in shape) + (1,) * (3 - len(shape))
         n = shape[0] * shape[1] * shape[2]
@@ -421,13 +425,17 @@ class Engine:
                                            nlabels, self.ptr(counts), self.ptr(dmax), self.ptr(first), self.ptr(xmin),
                                            self.ptr(xmax), self.ptr(yz), self.stream()))
         u32 = lambda x: x.cpu().numpy().view(np.uint32)
-        self.last_yz_extent = u32(yz).reshape(n1, 4)  # [ymin, ymax, zmin, zmax] per label (bounding boxes)
-        return u32(counts), dmax.cpu().numpy(), u32(first), u32(xmin), u32(xmax)
+        return LabelStats(u32(counts), dmax.cpu().numpy(), u32(first), u32(xmin), u32(xmax), u32(yz).reshape(n1, 4))
+
+    @staticmethod
+    def box(d, shape, lo, hi):
+        """the box [lo, hi) (x, y, z) of a device volume as a device view indexed [z, y, x]: torch C order (z, y, x) == Fortran
+        order (x, y, z).  Writing through it writes the volume."""
+        return d.view(shape[2], shape[1], shape[0])[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
 
     def crop(self, d, shape, lo, hi, dtype=np.uint32):
         """host copy of the box [lo, hi) of a device volume, as an (x, y, z) Fortran-ordered array."""
-        v = d.view(shape[2], shape[1], shape[0])[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
-        return np.asfortranarray(v.contiguous().cpu().numpy().view(dtype).transpose(2, 1, 0))
+        return np.asfortranarray(self.box(d, shape, lo, hi).contiguous().cpu().numpy().view(dtype).transpose(2, 1, 0))
 
     # -- level table of the order-free invalidation sweep (csrc/sweep.h) -------------
     def level_table(self, shape, anisotropy, rmax):
@@ -473,21 +481,21 @@ class Engine:
         d_cc = self.to_device(cc)
         d_dbf = self.to_device(np.asfortranarray(dbf, dtype=np.float32).reshape(shape, order="F")) if dbf is not None \
             else t.zeros(nvox, dtype=t.float32, device=self.device)
-        counts, dbf_max, first, xmin, xmax = self.label_stats(d_cc, 4, d_dbf, shape, 1)
-        cnt = int(counts[1])
+        stats = self.label_stats(d_cc, 4, d_dbf, shape, 1)
+        cnt = int(stats.counts[1])
         task = np.zeros(1, dtype=_abi.LABEL_T)
         task["segid"] = 1
         task["count"] = cnt
         # the reference runs on the array it is given: the x faces of THAT array matter to the heap order
         # (dijkstra_invalidation.hpp:116-123), not the object's own extent
         task["xmin"], task["xmax"] = 0, shape[0] - 1
-        task["source"] = first[1]
+        task["source"] = stats.first_index[1]
         task["root"] = NONE32
         task["q_capacity"] = cnt + 64
         hcap = 27 * cnt + 4096          # every push of the flood fits: a voxel is pushed by at most 26 neighbours (and the sweep's lists)
         task["heap_capacity"] = hcap
         task["path_capacity"] = 4 * cnt + 1024
-        ctx = {"shape": shape, "nvox": nvox, "count": cnt, "d_cc": d_cc, "d_dbf": d_dbf, "dbf_max": float(dbf_max[1])}
+        ctx = {"shape": shape, "nvox": nvox, "count": cnt, "d_cc": d_cc, "d_dbf": d_dbf, "dbf_max": float(stats.dbf_max[1])}
         d_slot = t.from_numpy(np.array([-1, 0], dtype=np.int32)).to(self.device)
         d_off = t.zeros(1, dtype=t.int32, device=self.device)
         d_cur = self.empty(1, t.int32)

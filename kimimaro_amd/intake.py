@@ -305,7 +305,6 @@ def connect_points(labels, start, end, anisotropy=(1, 1, 1), fill_holes=False, i
     from .trace import point_to_point
     eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     d_cc, _, _ = compute_cc_labels_device(eng, labels)
-    eng._narrow = None                               # (the u16 copy of the component ids is not kept alive past this call)
     cc = LazyVolume(eng, d_cc, labels.shape)
     if cc[start] == 0 or cc[start] != cc[end]:
         raise ValueError("Cannot extract centerline from disconnected components.")
@@ -355,7 +354,6 @@ def engage_avocado_protection_device(eng, d_cc, shape, nlabels, remapping, aniso
     d_cc = d_cc.clone()                      # (the caller's volume may be shared)
     orig = d_cc.clone()
     v = d_cc.view(sz, sy, sx)                # torch C order (z, y, x) == Fortran order (x, y, z)
-    eng._narrow = None                       # the u16 copy kh_ccl26 made no longer matches what is edited here
     d_dbf = eng.edt(d_cc, 4, shape, anisotropy, black_border)
     thr = float(np.float32(soma_detection_threshold / 2.5))     # numpy compares the f32 field with the scalar in float32
     unchanged = set()
@@ -367,13 +365,10 @@ def engage_avocado_protection_device(eng, d_cc, shape, nlabels, remapping, aniso
         order = [label for label in candidates if label != 0]
         changed, unchanged_now = set(), set()          # (the sets of ONE pass, intake.py:650-651)
         if order:
-            counts, _, _, xmin, xmax = eng.label_stats(d_cc, 4, d_dbf, shape, nlabels)
-            yz = eng.last_yz_extent
-            dv = d_dbf.view(sz, sy, sx)
+            stats = eng.label_stats(d_cc, 4, d_dbf, shape, nlabels)
             for label in order:
-                lo = (int(xmin[label]), int(yz[label, 0]), int(yz[label, 2]))
-                hi = (int(xmax[label]) + 1, int(yz[label, 1]) + 1, int(yz[label, 3]) + 1)
-                sub = v[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+                lo, hi = stats.bbox(label)
+                sub = eng.box(d_cc, shape, lo, hi)
                 binimg = (sub == label)
                 # paint_walls (:655-666): a 2-D fill on each of the six faces, in the reference's order
                 for face in ((-1, 0), (-1, -1), (1, 0), (1, -1), (2, 0), (2, -1)):      # (torch axis, index): z, z, y, y, x, x
@@ -383,7 +378,7 @@ def engage_avocado_protection_device(eng, d_cc, shape, nlabels, remapping, aniso
                     filled, nfill = eng.fill_voids(p2.view(-1), (p2.shape[1], p2.shape[0], 1), ndim=2)
                     if nfill:
                         plane.copy_(filled.view(p2.shape).bool())
-                prod = binimg * dv[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+                prod = binimg * eng.box(d_dbf, shape, lo, hi)
                 k = int(t.argmax(prod.reshape(-1)).item())            # first maximum in the raster (x fastest), like argmax(arr.T)
                 nx, ny = hi[0] - lo[0], hi[1] - lo[1]
                 cx, cy, cz = lo[0] + k % nx, lo[1] + (k // nx) % ny, lo[2] + k // (nx * ny)
@@ -435,22 +430,19 @@ def fill_all_holes_device(eng, d_cc, shape, nlabels):
     component are filled with kh_fill_voids on the component's bounding box, in ascending label order; a component
     that gets swallowed is not processed itself any more.  Bounding boxes are those before any filling, as in the
     reference (find_objects is called once, intake.py:767).  Returns the number of voxels filled."""
-    eng._narrow = None     # the component volume is edited in place below: its u16 copy no longer matches
+    eng.edited(d_cc)
     t = eng.torch
     nvox = int(shape[0]) * int(shape[1]) * int(shape[2])
-    counts, _, _, xmin, xmax = eng.label_stats(d_cc, 4, t.zeros(nvox, dtype=t.float32, device=eng.device), shape, nlabels)
-    yz = eng.last_yz_extent
+    stats = eng.label_stats(d_cc, 4, t.zeros(nvox, dtype=t.float32, device=eng.device), shape, nlabels)
     in_set = np.ones(nlabels + 1, dtype=bool)
     in_set[0] = False
-    v = d_cc.view(shape[2], shape[1], shape[0])      # torch C order (z, y, x) == F order (x, y, z)
     filled_total = 0
     for label in range(1, nlabels + 1):
-        if not in_set[label] or counts[label] == 0:
+        if not in_set[label] or stats.counts[label] == 0:
             continue
-        lo = (int(xmin[label]), int(yz[label, 0]), int(yz[label, 2]))
-        hi = (int(xmax[label]) + 1, int(yz[label, 1]) + 1, int(yz[label, 3]) + 1)
+        lo, hi = stats.bbox(label)
         cshape = (hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2])
-        sub = v[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+        sub = eng.box(d_cc, shape, lo, hi)
         d_filled, n = eng.fill_voids((sub == label).to(t.uint8).contiguous().view(-1), cshape)
         if n == 0:
             continue
@@ -551,15 +543,6 @@ def skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotropy
                    fix_branching, fix_borders, before, after, black_border, timings=None,
                    rank=0, world=1, d_cc=None, d_dbf=None, d_graph=None):
     """Everything after the connected components (intake.py:174-221 + skeletonize_subset :434-517)."""
-    try:
-        return _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotropy, dust_threshold, fix_branching,
-                               fix_borders, before, after, black_border, timings, rank, world, d_cc, d_dbf, d_graph)
-    finally:
-        eng._narrow = None      # the u16 copy of this volume's ids (2 B / voxel of HBM) is not kept alive past the call
-
-
-def _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotropy, dust_threshold,
-                    fix_branching, fix_borders, before, after, black_border, timings, rank, world, d_cc, d_dbf=None, d_graph=None):
     import time as _time
 
     def _mark(name):
@@ -582,10 +565,8 @@ def _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotrop
         d_dbf = eng.edt_graph(d_lab, label_bytes, d_graph, shape, anisotropy, black_border)  # intake.py:174-185 with voxel_graph
     if d_dbf is None:         # (fix_avocados hands over the transform of the components it left behind)
         d_dbf = eng.edt(d_lab, label_bytes, shape, anisotropy, black_border)  # intake.py:174-185
-    counts, dbf_max, first_index, xmin, xmax = eng.label_stats(d_lab, label_bytes, d_dbf, shape, nlabels)
-    yz = eng.last_yz_extent
-    bbox = lambda sid: ((int(xmin[sid]), int(yz[sid, 0]), int(yz[sid, 2])),
-                        (int(xmax[sid]) + 1, int(yz[sid, 1]) + 1, int(yz[sid, 3]) + 1))  # find_objects, utility.py:85-102
+    stats = eng.label_stats(d_lab, label_bytes, d_dbf, shape, nlabels)
+    counts, dbf_max = stats.counts, stats.dbf_max
     _mark("edt+stats")
 
     # intake.py:198-201
@@ -616,7 +597,7 @@ def _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotrop
         if segid in after and len(after[segid]) > 0:
             mta.extend(_loc(p, shape) for p in after[segid])
         if dbf_max[segid] > params["soma_detection_threshold"] and _needs_soma_path(
-                eng, d_cc, shape, bbox(segid), segid, float(dbf_max[segid]), params):
+                eng, d_cc, shape, stats.bbox(segid), segid, float(dbf_max[segid]), params):
             soma_jobs.append((segid, root, mtb, mta))  # traced one by one on their crop, below
             continue
         segids.append(segid)
@@ -625,20 +606,19 @@ def _skeletonize_cc(eng, cc_labels, nlabels, remapping, teasar_params, anisotrop
         ta.append(mta)
 
     if not soma_jobs and label_bytes == 2 and d_lab is not d_cc and os.environ.get("KH_KEEP_CC", "0") != "1":
-        # nothing reads the u32 ids any more (the faces are taken, no soma crop will be asked for): the u16 copy serves from here on
+        # nothing reads the u32 ids any more (the faces are taken, no soma crop will be asked for): the u16 copy, which d_lab holds,
+        # serves from here on
         d_cc = None
         cc_labels.release_device()
-        if getattr(eng, "_narrow", None) is not None:
-            eng._narrow = (None, eng._narrow[1])
     sel = np.asarray(segids, dtype=np.int64)
     asm = Assembler(shape, anisotropy, remapping)
-    labels = LabelSet(sel, counts[sel], dbf_max[sel], first_index[sel], xmin[sel], xmax[sel], roots, tb, ta)
+    labels = LabelSet(sel, counts[sel], dbf_max[sel], stats.first_index[sel], stats.xmin[sel], stats.xmax[sel], roots, tb, ta)
     eng.run_labels(d_lab, label_bytes, d_dbf, shape, anisotropy, nlabels, labels, params, fix_branching=fix_branching,
                    max_paths=params.get("max_paths"), timings=timings, consume=asm.add, voxel_graph=d_graph)
     out = asm.finish()
     _mark("assemble")
     if soma_jobs:
-        _trace_soma_labels(eng, soma_jobs, d_cc, d_dbf, shape, anisotropy, remapping, params, fix_branching, bbox, out, d_graph)
+        _trace_soma_labels(eng, soma_jobs, d_cc, d_dbf, shape, anisotropy, remapping, params, fix_branching, stats.bbox, out, d_graph)
         _mark("soma_labels")
     return out
 
@@ -699,8 +679,7 @@ def _needs_soma_path(eng, d_cc, shape, box, segid, dbf_max, params):
     t = eng.torch
     lo, hi = box
     cshape = (hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2])
-    v = d_cc.view(shape[2], shape[1], shape[0])[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
-    d_mask = (v == int(segid)).to(t.uint8).contiguous().view(-1)   # torch C order (z, y, x) == F order (x, y, z)
+    d_mask = (eng.box(d_cc, shape, lo, hi) == int(segid)).to(t.uint8).contiguous().view(-1)
     _, nfilled = eng.fill_voids(d_mask, cshape)
     return nfilled > 0
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 
@@ -174,6 +175,22 @@ class LabelSet:
         return LabelSet(self.segid[idx], self.count[idx], self.dbf_max[idx], self.first_index[idx], self.xmin[idx], self.xmax[idx],
                         self.root[idx], pick(self.targets_before), pick(self.targets_after),
                         None if self.soma is None else {k: v[idx] for k, v in self.soma.items()})
+
+
+class LabelStats(NamedTuple):
+    """What kh_label_stats computes per component id 0..n, as host columns: counts, first_index, xmin, xmax (u32), dbf_max (f32) and
+    yz (u32 [n + 1, 4]: ymin, ymax, zmin, zmax).  An id without a voxel keeps the identities of the minima and maxima."""
+    counts: np.ndarray
+    dbf_max: np.ndarray
+    first_index: np.ndarray
+    xmin: np.ndarray
+    xmax: np.ndarray
+    yz: np.ndarray
+
+    def bbox(self, label):
+        """((x0, y0, z0), (x1, y1, z1)), half open, of a label that has voxels: scipy.ndimage.find_objects (kimimaro/utility.py:85-102)"""
+        y0, y1, z0, z1 = (int(v) for v in self.yz[label])
+        return (int(self.xmin[label]), y0, z0), (int(self.xmax[label]) + 1, y1 + 1, z1 + 1)
 
 
 def label_order(counts):

@@ -26,13 +26,13 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
     dbf = np.asfortranarray(DBF, dtype=np.float32)
     d_cc = eng.to_device(cc)
     d_dbf = eng.to_device(dbf)
-    counts, dbf_max, first_index, xmin, xmax = eng.label_stats(d_cc, 4, d_dbf, shape, 1)
-    if counts[1] == 0:
+    stats = eng.label_stats(d_cc, 4, d_dbf, shape, 1)
+    if stats.counts[1] == 0:
         return [] if return_paths else Skeleton()
     loc = lambda p: int(p[0]) + shape[0] * (int(p[1]) + shape[1] * int(p[2]))
     mtb = [loc(p) for p in (manual_targets_before or [])]
     mta = [loc(p) for p in (manual_targets_after or [])]
-    dmax = np.float32(dbf_max[1])
+    dmax = np.float32(stats.dbf_max[1])
     soma_mode = False
     d_graph = None
     if voxel_graph is not None:
@@ -53,8 +53,8 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
             d_dbf = eng.edt(d_cc, 4, shape, anisotropy, bool(np.all(cc))) if d_graph is None else \
                 eng.edt_graph(d_cc, 4, d_graph, shape, anisotropy, bool(np.all(cc)))
             dbf = d_dbf.cpu().numpy().reshape(shape, order="F")
-            counts, dbf_max, first_index, xmin, xmax = eng.label_stats(d_cc, 4, d_dbf, shape, 1)
-            dmax = np.float32(dbf_max[1])
+            stats = eng.label_stats(d_cc, 4, d_dbf, shape, 1)
+            dmax = np.float32(stats.dbf_max[1])
         soma_mode = bool(dmax > soma_acceptance_threshold)
     r = NONE32 if root is None else loc(root)
     soma = None
@@ -74,7 +74,7 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
     params.update(scale=scale, const=const, pdrf_scale=pdrf_scale, pdrf_exponent=pdrf_exponent)
     # the reference runs on the array it is given: the x faces of THAT array are where its neighbour enumeration degenerates
     # (dijkstra_invalidation.hpp:116-123), not the object's own extent (skeletonize crops every label to its box first)
-    labels = LabelSet([1], counts[1:2], dbf_max[1:2], first_index[1:2], [0], [shape[0] - 1], [r], [mtb], [mta], soma)
+    labels = LabelSet([1], stats.counts[1:2], stats.dbf_max[1:2], stats.first_index[1:2], [0], [shape[0] - 1], [r], [mtb], [mta], soma)
     res = eng.run_labels(d_cc, 4, d_dbf, shape, anisotropy, 1, labels, params, fix_branching=fix_branching, max_paths=max_paths,
                          return_fields=_return_raw, voxel_graph=d_graph)
     if _return_raw:

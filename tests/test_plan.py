@@ -220,3 +220,29 @@ def test_offsets_beyond_32_bits_are_refused():
     with pytest.raises(ValueError, match="event arena offsets exceed 32 bits"):
         plan_sweep(cnt, np.full(n, 100, dtype=np.float32), lv)
     assert plan_sweep(cnt[:n // 2], np.full(n // 2, 100, dtype=np.float32), {k: v[:n // 2] for k, v in lv.items()}).ev_total < 2 ** 32
+
+
+def test_label_stats_bbox_is_find_objects():
+    """LabelStats.bbox on the numpy restatement of kh_label_stats: a blob, a single voxel and a label that touches the far faces"""
+    import os
+    import sys
+    import scipy.ndimage
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import prep_ref
+    from kimimaro_amd.plan import LabelStats
+    lab = np.zeros((9, 7, 5), dtype=np.uint32, order="F")
+    lab[1:4, 2:6, 0:3] = 1
+    lab[2, 3, 1] = 0                    # (a hole changes no box)
+    lab[5, 1, 3] = 2                    # one voxel
+    lab[6:9, 4:7, 2:5] = 3              # up to the last voxel of every axis
+    dbf = np.random.default_rng(3).random(lab.shape).astype(np.float32)
+    stats = LabelStats(*prep_ref.label_stats(lab, dbf, 3))
+    assert stats._fields == ("counts", "dbf_max", "first_index", "xmin", "xmax", "yz")
+    assert stats.yz.shape == (4, 4) and stats.counts.tolist() == [0, 35, 1, 27]
+    boxes = scipy.ndimage.find_objects(lab)
+    assert len(boxes) == 3
+    for label in (1, 2, 3):
+        lo, hi = stats.bbox(label)
+        assert all(type(v) is int for v in lo + hi)
+        assert tuple(slice(a, b) for a, b in zip(lo, hi)) == boxes[label - 1]
+    assert stats.bbox(2) == ((5, 1, 3), (6, 2, 4)) and stats.bbox(3)[1] == lab.shape
