@@ -439,6 +439,16 @@ int kh_region_apply(const uint32_t* region, const uint64_t* owner, void* labels,
 #define KH_HOLES_KILLED 4      /* a region of the label lies in a hole that was filled (at any time) */
 int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value, const uint32_t* count, const uint8_t* face, int64_t npairs,
                               const uint64_t* pairs, uint64_t* owner, uint64_t* label_value, uint8_t* label_state, int64_t* filled);
+/* host (no GPU needed): hole(L) itself for each of n_labels wanted label words (labels: u64, any order, duplicates allowed, 0 is a
+ * value like any other), on the graph as given: no dead set, no order among the labels, so a region may be listed for several
+ * labels (a core inside shell B inside shell A lies in hole(A) and in hole(B)).  nregions / value / face / npairs / pairs as above.
+ * offsets (u64 [n_labels + 1]) is always set; regions (u32 [capacity]) receives for label i, at offsets[i] .. offsets[i + 1], the ids
+ * of hole(labels[i])'s regions, ascending; a label that does not occur or has no holes gets an empty range.
+ * Returns the total offsets[n_labels]; when it exceeds `capacity` NOTHING was written to regions: call again with a larger one
+ * (capacity 0 with regions == NULL asks for the size).  -1 on allocation failure, -2 on bad arguments (as above).
+ * These lists, expanded per item, are what kh_cross_sections_filled reads.                                                       */
+int64_t kh_host_enclosed_regions(int64_t nregions, const uint64_t* value, const uint8_t* face, int64_t npairs, const uint64_t* pairs,
+                                 int64_t n_labels, const uint64_t* labels, uint64_t* offsets, uint32_t* regions, int64_t capacity);
 
 /* ---- kimimaro.oversegment (kimimaro/utility.py:562-644) / dijkstra3d.euclidean_distance_field(..., return_feature_map=True) from
  * MANY sources: the geodesic Voronoi diagram of seed voxels inside every label, over the whole volume at once (csrc/feature.hip,
@@ -520,6 +530,18 @@ int kh_cross_sections(const void* labels, int label_bytes, int64_t sx, int64_t s
                       int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals, float* area,
                       uint8_t* contact, uint32_t* voxels, void* scratch, int64_t scratch_bytes, void* stream);
 int64_t kh_cross_sections_scratch_bytes(int64_t sx, int64_t sy, int64_t sz, int64_t n_waves);
+/* kimimaro.cross_sectional_area(fill_holes=True): the same sections of filled(L) = {labels == L} u hole(L) (hole(L) as defined at
+ * kh_regions6, ndim 3) -- "carries the label" becomes "lies in filled(label)", for the seed too: a seed in a hole voxel is valid.
+ * region: u32 [nvox], kh_regions6's output for the same label array; item i's holes are the region ids
+ * hole_regions[hole_begin[i] .. hole_begin[i] + hole_count[i]), ASCENDING (kh_host_enclosed_regions' list of the item's label; the
+ * caller expands label -> item).  An item with hole_count 0 reads no region and gives kh_cross_sections' outputs bit for bit.
+ * Everything else, the scratch and kh_cross_sections_scratch_bytes included, as kh_cross_sections; a null region / hole_begin /
+ * hole_count / hole_regions with n_items > 0 is a bad argument.                                                                 */
+int kh_cross_sections_filled(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay, double az,
+                             int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals,
+                             const uint32_t* region, const uint32_t* hole_begin, const uint32_t* hole_count,
+                             const uint32_t* hole_regions, float* area, uint8_t* contact, uint32_t* voxels, void* scratch,
+                             int64_t scratch_bytes, void* stream);
 /* host: the membership test and the area of ONE voxel at offset (dx, dy, dz) from the seed, by the functions the kernel runs
  * (normal, anisotropy: f64 [3]).  Returns 1 if the voxel is cut; *offset = d, *half_width = h, *area = area(plane /\ box).      */
 int kh_host_section_voxel(const double* normal, const double* anisotropy, int64_t dx, int64_t dy, int64_t dz, double* offset,

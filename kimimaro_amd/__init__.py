@@ -14,7 +14,7 @@ from .intake import DEFAULT_TEASAR_PARAMS, DimensionError, connect_points, skele
 from .lanes import skeletonize_many  # noqa: F401
 from .post import join_close_components, postprocess  # noqa: F401
 from .skeleton import Skeleton  # noqa: F401
-from .utility import (cross_sectional_area, cross_sectional_area_single, extract_skeleton_from_binary_image,  # noqa: F401
-                      oversegment)
+from .utility import (cross_sectional_area, cross_sectional_area_filled, cross_sectional_area_single,  # noqa: F401
+                      extract_skeleton_from_binary_image, oversegment)
 
 __version__ = "0.1.0"

@@ -22,8 +22,8 @@ SYMBOLS = [
     "kh_host_consolidate_paths",
     "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
     "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
-    "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel",
-    "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes",
+    "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
+    "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
 ]
 
 
@@ -165,17 +165,20 @@ def lib():
     L.kh_cross_sections_scratch_bytes.argtypes = [i64, i64, i64, i64]
     L.kh_cross_sections_scratch_bytes.restype = i64
     L.kh_host_section_voxel.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
+    L.kh_cross_sections_filled.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.kh_regions6.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp, vp]
     L.kh_region_table.argtypes = [vp, ci, vp, vp, i64, ci, i64, i64, i64, vp, vp, vp, vp]
     L.kh_region_pairs.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp]
     L.kh_region_apply.argtypes = [vp, vp, vp, ci, i64, vp]
     L.kh_host_resolve_holes.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.kh_host_resolve_holes.restype = i64
+    L.kh_host_enclosed_regions.argtypes = [i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]
+    L.kh_host_enclosed_regions.restype = i64
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",
                         "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths",
-                        "kh_host_resolve_holes"):
+                        "kh_host_resolve_holes", "kh_host_enclosed_regions"):
             getattr(L, name).restype = ci
     _lib = L
     return L

@@ -448,6 +448,83 @@ extern "C" int64_t kh_host_find_border_targets(const float* dt, const uint32_t* 
 }
 
 // ---- kimimaro.intake.fill_all_holes (kimimaro/intake.py:763-790) on the region adjacency graph (see kimi_hip.h)
+namespace {
+// the adjacency lists of the regions 1..R from the unordered pairs: the neighbours of r are adj[start[r] .. start[r + 1])
+struct RegionGraph {
+  std::vector<uint32_t> start, adj;
+  // false: a pair names a region outside 1..nregions, or joins a region with itself
+  bool build(int64_t nregions, int64_t npairs, const uint64_t* pairs) {
+    const size_t R = (size_t)nregions;
+    start.assign(R + 2, 0u);
+    adj.resize((size_t)(2 * npairs));
+    for (int64_t p = 0; p < npairs; p++) {
+      const uint64_t a = pairs[p] >> 32, b = pairs[p] & 0xFFFFFFFFull;
+      if (a < 1 || b < 1 || a > (uint64_t)nregions || b > (uint64_t)nregions || a == b) return false;
+      start[a + 1]++;
+      start[b + 1]++;
+    }
+    for (size_t r = 1; r <= R + 1; r++) start[r] += start[r - 1];
+    std::vector<uint32_t> at(start.begin(), start.end() - 1);
+    for (int64_t p = 0; p < npairs; p++) {
+      const uint32_t a = (uint32_t)(pairs[p] >> 32), b = (uint32_t)pairs[p];
+      adj[at[a]++] = b;
+      adj[at[b]++] = a;
+    }
+    return true;
+  }
+};
+
+// hole(L) on the graph: the regions that no path joins to a face-owning region once L's regions (the walls) are removed.
+// seen[r] == epoch: r is a wall of the label at hand or was reached by a search of this label; open[r] == epoch: it reaches a
+// face-owning region without crossing a wall.  A search ends at the first face-owning or open region it meets -- everything it
+// has seen so far is open then, and what it has not seen finds that out from there.  The stamps make a label cost about its
+// regions' degree (plus its holes), not the graph.
+struct HoleSearch {
+  const RegionGraph& g;
+  const uint8_t* face;
+  std::vector<uint32_t> seen, open, queue;
+  uint32_t epoch = 0;
+  HoleSearch(const RegionGraph& graph, const uint8_t* face_flags, size_t R) : g(graph), face(face_flags), seen(R + 1, 0u), open(R + 1, 0u) {}
+
+  // the component of s among the regions that are not walls (s not seen yet): appended to `holes` when it is closed
+  void component(uint32_t s, std::vector<uint32_t>& holes) {
+    queue.clear();
+    queue.push_back(s);
+    seen[s] = epoch;
+    bool is_open = face[s] != 0;
+    for (size_t head = 0; head < queue.size() && !is_open; head++) {
+      const uint32_t u = queue[head];
+      for (uint32_t f = g.start[u]; f < g.start[u + 1]; f++) {
+        const uint32_t v = g.adj[f];
+        if (seen[v] == epoch) {
+          if (open[v] == epoch) { is_open = true; break; }
+          continue;
+        }
+        seen[v] = epoch;
+        queue.push_back(v);
+        if (face[v] != 0) { is_open = true; break; }
+      }
+    }
+    if (is_open) for (uint32_t u : queue) open[u] = epoch;
+    else holes.insert(holes.end(), queue.begin(), queue.end());
+  }
+
+  // holes = the regions of hole(L), L's regions being walls[0 .. n), in the order the searches find them
+  void holes_of(const uint32_t* walls, size_t n, std::vector<uint32_t>& holes) {
+    if (++epoch == 0) {                                                  // (2^32 labels: start the stamps over)
+      std::fill(seen.begin(), seen.end(), 0u);
+      std::fill(open.begin(), open.end(), 0u);
+      epoch = 1;
+    }
+    for (size_t i = 0; i < n; i++) seen[walls[i]] = epoch;
+    holes.clear();
+    for (size_t i = 0; i < n; i++)
+      for (uint32_t e = g.start[walls[i]]; e < g.start[walls[i] + 1]; e++)
+        if (seen[g.adj[e]] != epoch) component(g.adj[e], holes);
+  }
+};
+}  // namespace
+
 extern "C" int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value, const uint32_t* count, const uint8_t* face,
                                          int64_t npairs, const uint64_t* pairs, uint64_t* owner, uint64_t* label_value,
                                          uint8_t* label_state, int64_t* filled) {
@@ -455,22 +532,8 @@ extern "C" int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value
     return -2;
   try {
     const size_t R = (size_t)nregions;
-    std::vector<uint32_t> start(R + 2, 0u), adj((size_t)(2 * npairs));
-    for (int64_t p = 0; p < npairs; p++) {
-      const uint64_t a = pairs[p] >> 32, b = pairs[p] & 0xFFFFFFFFull;
-      if (a < 1 || b < 1 || a > (uint64_t)nregions || b > (uint64_t)nregions || a == b) return -2;
-      start[a + 1]++;
-      start[b + 1]++;
-    }
-    for (size_t r = 1; r <= R + 1; r++) start[r] += start[r - 1];        // the neighbours of r: adj[start[r] .. start[r + 1])
-    {
-      std::vector<uint32_t> at(start.begin(), start.end() - 1);
-      for (int64_t p = 0; p < npairs; p++) {
-        const uint32_t a = (uint32_t)(pairs[p] >> 32), b = (uint32_t)pairs[p];
-        adj[at[a]++] = b;
-        adj[at[b]++] = a;
-      }
-    }
+    RegionGraph graph;
+    if (!graph.build(nregions, npairs, pairs)) return -2;
     // the regions of every non-zero value, values ascending
     std::vector<uint32_t> order;
     order.reserve(R);
@@ -493,48 +556,13 @@ extern "C" int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value
     const int64_t nlabels = (int64_t)first.size();
     first.push_back(order.size());
 
-    // seen[r] == epoch: r is a wall (a region of the label at hand) or was reached by a search of this label; open[r] == epoch: it
-    // reaches a face-owning region without crossing a wall.  A search ends at the first face-owning or open region it meets --
-    // everything it has seen so far is open then, and what it has not seen finds that out from there.
-    std::vector<uint32_t> seen(R + 1, 0u), open(R + 1, 0u), queue, holes;
-    uint32_t epoch = 0;
+    HoleSearch search(graph, face, R);
+    std::vector<uint32_t> holes;
     int64_t total = 0;
     for (int64_t k = 0; k < nlabels; k++) {
       if (label_state[k] & KH_HOLES_KILLED) continue;
       label_state[k] |= KH_HOLES_PROCESSED;
-      if (++epoch == 0) {                                                // (2^32 labels: start the stamps over)
-        std::fill(seen.begin(), seen.end(), 0u);
-        std::fill(open.begin(), open.end(), 0u);
-        epoch = 1;
-      }
-      for (size_t i = first[(size_t)k]; i < first[(size_t)k + 1]; i++) seen[order[i]] = epoch;
-      holes.clear();
-      for (size_t i = first[(size_t)k]; i < first[(size_t)k + 1]; i++) {
-        const uint32_t wall = order[i];
-        for (uint32_t e = start[wall]; e < start[wall + 1]; e++) {
-          const uint32_t s = adj[e];
-          if (seen[s] == epoch) continue;
-          queue.clear();
-          queue.push_back(s);
-          seen[s] = epoch;
-          bool is_open = face[s] != 0;
-          for (size_t head = 0; head < queue.size() && !is_open; head++) {
-            const uint32_t u = queue[head];
-            for (uint32_t f = start[u]; f < start[u + 1]; f++) {
-              const uint32_t v = adj[f];
-              if (seen[v] == epoch) {
-                if (open[v] == epoch) { is_open = true; break; }
-                continue;
-              }
-              seen[v] = epoch;
-              queue.push_back(v);
-              if (face[v] != 0) { is_open = true; break; }
-            }
-          }
-          if (is_open) for (uint32_t u : queue) open[u] = epoch;
-          else holes.insert(holes.end(), queue.begin(), queue.end());
-        }
-      }
+      search.holes_of(order.data() + first[(size_t)k], first[(size_t)k + 1] - first[(size_t)k], holes);
       if (holes.empty()) continue;
       label_state[k] |= KH_HOLES_FILLED;
       for (uint32_t h : holes) {
@@ -545,6 +573,42 @@ extern "C" int64_t kh_host_resolve_holes(int64_t nregions, const uint64_t* value
     }
     *filled = total;
     return nlabels;
+  } catch (const std::bad_alloc&) {
+    return -1;
+  }
+}
+
+// hole(L) for each of n_labels wanted label words, on the input graph: no dead set, no order among the labels (see kimi_hip.h)
+extern "C" int64_t kh_host_enclosed_regions(int64_t nregions, const uint64_t* value, const uint8_t* face, int64_t npairs,
+                                            const uint64_t* pairs, int64_t n_labels, const uint64_t* labels, uint64_t* offsets,
+                                            uint32_t* regions, int64_t capacity) {
+  if (nregions < 0 || npairs < 0 || n_labels < 0 || capacity < 0 || !value || !face || (npairs && !pairs) || (n_labels && !labels) ||
+      !offsets || (capacity && !regions))
+    return -2;
+  try {
+    const size_t R = (size_t)nregions;
+    RegionGraph graph;
+    if (!graph.build(nregions, npairs, pairs)) return -2;
+    // the regions of every value (0 is a value like any other here), values ascending
+    std::vector<uint32_t> order(R);
+    for (size_t r = 1; r <= R; r++) order[r - 1] = (uint32_t)r;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return value[a] != value[b] ? value[a] < value[b] : a < b; });
+    HoleSearch search(graph, face, R);
+    std::vector<uint32_t> holes, all;
+    offsets[0] = 0;
+    for (int64_t i = 0; i < n_labels; i++) {
+      const uint64_t L = labels[i];
+      const auto lo = std::lower_bound(order.begin(), order.end(), L, [&](uint32_t r, uint64_t v) { return value[r] < v; });
+      const auto hi = std::upper_bound(lo, order.end(), L, [&](uint64_t v, uint32_t r) { return v < value[r]; });
+      if (lo != hi) {
+        search.holes_of(&*lo, (size_t)(hi - lo), holes);
+        std::sort(holes.begin(), holes.end());
+        all.insert(all.end(), holes.begin(), holes.end());
+      }
+      offsets[i + 1] = (uint64_t)all.size();
+    }
+    if ((int64_t)all.size() <= capacity) std::copy(all.begin(), all.end(), regions);
+    return (int64_t)all.size();
   } catch (const std::bad_alloc&) {
     return -1;
   }

@@ -17,6 +17,10 @@
 //             largest possible sum: integer sums do not depend on the order in which the flood arrives.
 //
 // Membership is the statement of DESIGN.md 3.12, operation by operation (this library is built with -ffp-contract=off).
+//
+// The FILLED instantiation (kh_cross_sections_filled) cuts filled(L) = L u hole(L) instead of L: "carries the item's label" becomes
+// "carries it, or lies in one of the regions (kh_regions6) that the item's sorted list names".  Only that test differs; an item
+// with an empty list reads no region at all.
 #include <math.h>
 
 #include "common.h"
@@ -99,8 +103,27 @@ struct XsArgs {
   double fixed_scale, fixed_inverse;   // 2^k and 2^-k of the fixed point
 };
 
-template <typename LT>
-__global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel(const LT* __restrict__ lab, XsArgs p) {
+// the holes of the items' labels (FILLED): item i's regions are list[begin[i] .. begin[i] + count[i]), ascending
+struct XsHoles {
+  const uint32_t* region;        // [nvox]: kh_regions6
+  const uint32_t* begin;
+  const uint32_t* count;
+  const uint32_t* list;
+};
+
+// is r among list[0 .. n) (ascending)?
+__device__ inline bool xs_listed(const uint32_t* __restrict__ list, uint32_t n, uint32_t r) {
+  uint32_t lo = 0, hi = n;       // the first entry >= r lies in [lo, hi]
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (list[mid] < r) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && list[lo] == r;
+}
+
+template <typename LT, bool FILLED>
+__global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel(const LT* __restrict__ lab, XsArgs p, XsHoles hs) {
   __shared__ uint32_t lds_queue[XS_WAVES_PER_BLOCK][XS_LDS_QUEUE];
   const int lane = (int)(threadIdx.x & 63);
   const int wave_in_block = (int)(threadIdx.x >> 6);
@@ -123,7 +146,22 @@ __global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel
     const double nx = p.normals[3 * item + 0], ny = p.normals[3 * item + 1], nz = p.normals[3 * item + 2];
     const double h = xs_half_width(nx, ny, nz, p.ax, p.ay, p.az);
     bool valid = (int64_t)seed < nvox && isfinite(nx) && isfinite(ny) && isfinite(nz) && h > 0.0 && isfinite(h);
-    if (valid) valid = (uint32_t)lab[seed] == want;
+    // (FILLED) the item's holes: n_holes == 0 is wave uniform and keeps every region load away
+    const uint32_t* holes = nullptr;
+    uint32_t n_holes = 0, hole_min = 0, hole_max = 0;
+    if (FILLED) {
+      n_holes = hs.count[item];
+      if (n_holes) {
+        holes = hs.list + hs.begin[item];
+        hole_min = holes[0];
+        hole_max = holes[n_holes - 1];
+      }
+    }
+    auto in_hole = [&](uint32_t r) -> bool { return r >= hole_min && r <= hole_max && xs_listed(holes, n_holes, r); };
+    if (valid) {
+      valid = (uint32_t)lab[seed] == want;
+      if (FILLED && !valid && n_holes) valid = in_hole(hs.region[seed]);
+    }
     if (!valid) {       // (wave uniform)
       if (lane == 0) {
         p.area[item] = 0.0f;
@@ -177,7 +215,7 @@ __global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel
         touch |= (x == 0 ? 1u : 0u) | (x == p.sx - 1 ? 2u : 0u) | (y == 0 ? 4u : 0u) | (y == p.sy - 1 ? 8u : 0u) |
                  (z == 0 ? 16u : 0u) | (z == p.sz - 1 ? 32u : 0u);
         // every neighbour's label in flight at once: a neighbour that is outside or not cut reads the voxel itself instead
-        uint32_t same = 0;
+        uint32_t same = 0, other = 0;      // other (FILLED): cut neighbours that carry another label
 #pragma unroll
         for (int k = 0; k < 27; k++) {
           if (k == 13) continue;
@@ -189,6 +227,23 @@ __global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel
           const int64_t at = ok ? (int64_t)qx + (int64_t)p.sx * ((int64_t)qy + (int64_t)p.sy * qz) : (int64_t)self;
           const uint32_t l = (uint32_t)lab[at];
           same |= (ok && l == want) ? 1u << k : 0u;
+          if (FILLED) other |= (ok && l != want) ? 1u << k : 0u;
+        }
+        if (FILLED && n_holes) {
+          // their regions, all loads in flight at once as the labels above (a neighbour that is not asked reads nothing), then
+          // the searches
+          uint32_t rid[27];
+#pragma unroll
+          for (int k = 0; k < 27; k++) {
+            if (k == 13) continue;
+            const int64_t at = (int64_t)(x + k % 3 - 1) + (int64_t)p.sx * ((int64_t)(y + (k / 3) % 3 - 1) + (int64_t)p.sy * (z + k / 9 - 1));
+            rid[k] = (other >> k & 1u) ? hs.region[at] : 0u;
+          }
+#pragma unroll
+          for (int k = 0; k < 27; k++) {
+            if (k == 13) continue;
+            if ((other >> k & 1u) && in_hole(rid[k])) same |= 1u << k;
+          }
         }
         while (same) {
           const int k = __ffs((int)same) - 1;
@@ -274,28 +329,33 @@ extern "C" int64_t kh_cross_sections_scratch_bytes(int64_t sx, int64_t sy, int64
   return XS_HEADER_BYTES + n_waves * L.wave_bytes;
 }
 
-extern "C" int kh_cross_sections(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
-                                 double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
-                                 const double* normals, float* area, uint8_t* contact, uint32_t* voxels, void* scratch,
-                                 int64_t scratch_bytes, void* stream) {
+// both entry points: hs == nullptr launches the plain instantiation, `name` heads the error messages
+static int xs_launch(const char* name, const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                     double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals,
+                     const XsHoles* hs, float* area, uint8_t* contact, uint32_t* voxels, void* scratch, int64_t scratch_bytes,
+                     void* stream) {
   if (int rc = require_device()) return rc;
   XsLayout L;
   if (!xs_layout(sx, sy, sz, L)) {
-    set_error("kh_cross_sections: extents in [1, 2^31), fewer than 2^32 - 1 voxels");
+    set_error("%s: extents in [1, 2^31), fewer than 2^32 - 1 voxels", name);
     return KH_EINVAL;
   }
   if (!(ax > 0 && ay > 0 && az > 0) || !isfinite(ax) || !isfinite(ay) || !isfinite(az)) {
-    set_error("kh_cross_sections: the anisotropy must be three finite positive numbers");
+    set_error("%s: the anisotropy must be three finite positive numbers", name);
     return KH_EINVAL;
   }
   if (n_items < 0 || n_items >= (1ll << 32)) {
-    set_error("kh_cross_sections: 0 <= n_items < 2^32");
+    set_error("%s: 0 <= n_items < 2^32", name);
     return KH_EINVAL;
   }
   if (n_items == 0) return KH_OK;
+  if (hs && (!hs->region || !hs->begin || !hs->count || !hs->list)) {
+    set_error("%s: region, hole_begin, hole_count and hole_regions must not be null", name);
+    return KH_EINVAL;
+  }
   int64_t waves = (scratch_bytes - XS_HEADER_BYTES) / L.wave_bytes;
   if (scratch_bytes < XS_HEADER_BYTES || waves < 1 || ((uintptr_t)scratch & 7)) {
-    set_error("kh_cross_sections: the scratch holds no wave (kh_cross_sections_scratch_bytes) or is not 8-byte aligned");
+    set_error("%s: the scratch holds no wave (kh_cross_sections_scratch_bytes) or is not 8-byte aligned", name);
     return KH_EINVAL;
   }
   if (waves > n_items) waves = n_items;
@@ -322,14 +382,40 @@ extern "C" int kh_cross_sections(const void* labels, int label_bytes, int64_t sx
   p.fixed_inverse = ldexp(1.0, e - 62);
   KH_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(XS_HEADER_BYTES + waves * L.bitmap_words * 4), st));
   const unsigned grid = (unsigned)((waves + XS_WAVES_PER_BLOCK - 1) / XS_WAVES_PER_BLOCK);
+  const dim3 block(64 * XS_WAVES_PER_BLOCK);
+  const XsHoles none = {nullptr, nullptr, nullptr, nullptr};
+#define KH_XS_LAUNCH(LT)                                                                                                  \
+  do {                                                                                                                    \
+    if (hs) hipLaunchKernelGGL((cross_sections_kernel<LT, true>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs);    \
+    else hipLaunchKernelGGL((cross_sections_kernel<LT, false>), dim3(grid), block, 0, st, (const LT*)labels, p, none);     \
+  } while (0)
   switch (label_bytes) {
-    case 1: hipLaunchKernelGGL(cross_sections_kernel<uint8_t>, dim3(grid), dim3(64 * XS_WAVES_PER_BLOCK), 0, st, (const uint8_t*)labels, p); break;
-    case 2: hipLaunchKernelGGL(cross_sections_kernel<uint16_t>, dim3(grid), dim3(64 * XS_WAVES_PER_BLOCK), 0, st, (const uint16_t*)labels, p); break;
-    case 4: hipLaunchKernelGGL(cross_sections_kernel<uint32_t>, dim3(grid), dim3(64 * XS_WAVES_PER_BLOCK), 0, st, (const uint32_t*)labels, p); break;
-    default: set_error("kh_cross_sections: label_bytes must be 1, 2 or 4"); return KH_EINVAL;
+    case 1: KH_XS_LAUNCH(uint8_t); break;
+    case 2: KH_XS_LAUNCH(uint16_t); break;
+    case 4: KH_XS_LAUNCH(uint32_t); break;
+    default: set_error("%s: label_bytes must be 1, 2 or 4", name); return KH_EINVAL;
   }
+#undef KH_XS_LAUNCH
   KH_LAUNCH_CHECK();
   return KH_OK;
+}
+
+extern "C" int kh_cross_sections(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                                 double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                 const double* normals, float* area, uint8_t* contact, uint32_t* voxels, void* scratch,
+                                 int64_t scratch_bytes, void* stream) {
+  return xs_launch("kh_cross_sections", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, nullptr,
+                   area, contact, voxels, scratch, scratch_bytes, stream);
+}
+
+extern "C" int kh_cross_sections_filled(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                                        double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                        const double* normals, const uint32_t* region, const uint32_t* hole_begin,
+                                        const uint32_t* hole_count, const uint32_t* hole_regions, float* area, uint8_t* contact,
+                                        uint32_t* voxels, void* scratch, int64_t scratch_bytes, void* stream) {
+  const XsHoles hs = {region, hole_begin, hole_count, hole_regions};
+  return xs_launch("kh_cross_sections_filled", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, &hs,
+                   area, contact, voxels, scratch, scratch_bytes, stream);
 }
 
 // host: the membership test and the per-voxel area of one voxel at offset (dx, dy, dz) from the seed -- the same inline functions

@@ -484,6 +484,35 @@ def resolve_holes(value, count, face, pairs):
     return owner, label_value[:nlab], label_state[:nlab], int(filled.value)
 
 
+def enclosed_regions(value, face, pairs, labels):
+    """kh_host_enclosed_regions (host C, no GPU needed): hole(L) for each of the wanted label words `labels` (u64, any order,
+    duplicates allowed) on the region adjacency graph as given -- no dead set, no order among the labels, a region may be listed for
+    several labels.  value (u64), face (u8), pairs (u64): as resolve_holes takes them.
+    Returns (offsets u64 [len(labels) + 1], regions u32): label i's hole regions are regions[offsets[i]:offsets[i + 1]], ascending;
+    empty for a label that does not occur or has no holes."""
+    import ctypes as C
+    lib = _abi.lib()
+    value = np.ascontiguousarray(value, dtype=np.uint64)
+    face = np.ascontiguousarray(face, dtype=np.uint8)
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
+    labels = np.ascontiguousarray(labels, dtype=np.uint64)
+    if not (value.ndim == face.ndim == pairs.ndim == labels.ndim == 1 and value.size == face.size >= 1):
+        raise ValueError("value and face are 1-D arrays of one length (regions + 1), pairs and labels are 1-D")
+    offsets = np.zeros(labels.size + 1, dtype=np.uint64)
+    regions = np.zeros(0, dtype=np.uint32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    while True:                                      # the first call asks for the size, the second one fills
+        total = lib.kh_host_enclosed_regions(value.size - 1, p(value), p(face), pairs.size, p(pairs), labels.size, p(labels), p(offsets),
+                                             p(regions), regions.size)
+        if total == -1:
+            raise MemoryError("kh_host_enclosed_regions failed")
+        if total < 0:
+            raise ValueError("kh_host_enclosed_regions: a pair names a region outside 1..%d, or joins a region with itself" % (value.size - 1))
+        if total <= regions.size:
+            return offsets, regions[:total]
+        regions = np.zeros(total, dtype=np.uint32)
+
+
 def fill_all_holes(cc_labels, progress=False, return_fill_count=False):
     """kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795): fills the holes of every label and removes the labels that get
     filled in.  A hole of L is what fill_voids.fill paints on L's bounding box: the voxels that no 6-connected path outside L joins

@@ -21,11 +21,50 @@ def seed_index(vox, shape):
     return np.where(inside, lin, OUTSIDE).astype(np.uint32)
 
 
-def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, normals, stats=None):
+def hole_tables(eng, d_lab, label_bytes, shape, words, stats=None):
+    """What cross_sections(filled=...) needs for sections of filled(L) = L u hole(L), made once per volume:
+    the regions of the label volume (Engine.region_graph, ndim 3) and hole(L) for every device label word in `words`
+    (kh_host_enclosed_regions).  Returns (d_region: u32 region id per voxel, resident; word_range: {word: (begin, count)} into
+    d_hole_regions: the lists, resident, never empty so that it has an address).  Resident: 4 bytes per voxel plus the lists.
+    stats (a dict) receives region_graph's info, enclosed_ms (the host search), csr_regions and labels_with_holes."""
+    import time
+    from .intake import enclosed_regions
+    t = eng.torch
+    marks = []
+
+    def mark(name):
+        if stats is not None:
+            ev = t.cuda.Event(enable_timing=True)
+            ev.record(t.cuda.current_stream(eng.device))
+            marks.append((name, ev))
+
+    d_region, value, _, face, pairs, info = eng.region_graph(d_lab, label_bytes, tuple(int(v) for v in shape), 3, mark)
+    words = sorted(set(int(w) for w in words))
+    t0 = time.perf_counter()
+    offsets, regions = enclosed_regions(value, face, pairs, np.array(words, dtype=np.uint64))
+    t1 = time.perf_counter()
+    if regions.size >= 2 ** 32:
+        raise ValueError("fewer than 2^32 hole regions in all")
+    word_range = {w: (int(offsets[k]), int(offsets[k + 1] - offsets[k])) for k, w in enumerate(words)}
+    host = regions if regions.size else np.zeros(1, dtype=np.uint32)
+    d_hole_regions = t.from_numpy(host.view(np.int32).copy()).to(eng.device)
+    if stats is not None:
+        stats.update(info, enclosed_ms=(t1 - t0) * 1e3, csr_regions=int(regions.size),
+                     labels_with_holes=sum(1 for w in words if word_range[w][1]))
+        eng.sync_stream()
+        for (name, a), (_, b) in zip(marks[0::2], marks[1::2]):
+            stats[name + "_ms"] = stats.get(name + "_ms", 0.0) + a.elapsed_time(b)
+    return d_region, word_range, d_hole_regions
+
+
+def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, normals, stats=None, filled=None):
     """d_lab: the label volume on the device (1-D, Fortran order, label_bytes 1 / 2 / 4); seed_lin, want_label: u32 [n] (seed_index;
     the unsigned word the section's voxels carry); normals: f64 [n, 3], any length.  Returns host arrays (area f32 [n], contact u8
     [n], voxels u32 [n]): kh_cross_sections' outputs.  stats (a dict) receives the kernel's milliseconds (HIP events), the items and
-    the waves of the launch, accumulated over calls."""
+    the waves of the launch, accumulated over calls.
+    filled = (d_region, hole_begin, hole_count, d_hole_regions) selects kh_cross_sections_filled, the sections of filled(label):
+    d_region u32 [nvox] on the device (kh_regions6 on d_lab), hole_begin / hole_count u32 [n] on the host (item i's holes are
+    d_hole_regions[hole_begin[i] : hole_begin[i] + hole_count[i]], ascending region ids; hole_tables makes them per label)."""
     t, P = eng.torch, eng.ptr
     sx, sy, sz = (int(v) for v in shape)
     an = np.asarray(anisotropy, dtype=np.float64).reshape(-1)
@@ -36,6 +75,15 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
     normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
     n = int(seed_lin.size)
     assert want_label.size == n and normals.shape[0] == n
+    if filled is not None:
+        d_region, hole_begin, hole_count, d_hole_regions = filled
+        hole_begin = np.ascontiguousarray(hole_begin, dtype=np.uint32).reshape(-1)
+        hole_count = np.ascontiguousarray(hole_count, dtype=np.uint32).reshape(-1)
+        assert hole_begin.size == n and hole_count.size == n
+        if int(d_region.numel()) != sx * sy * sz or d_region.element_size() != 4:
+            raise ValueError("region: one u32 per voxel (kh_regions6)")
+        if n and int((hole_begin.astype(np.int64) + hole_count).max()) > int(d_hole_regions.numel()):
+            raise ValueError("a hole range ends behind the region list")
     if n == 0:
         return np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32)
     if label_bytes not in (1, 2, 4):
@@ -56,9 +104,17 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
         stream = t.cuda.current_stream(eng.device)
         before, after = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
         before.record(stream)
-    _abi.check(eng.lib.kh_cross_sections(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n, P(d_seed),
-                                         P(d_want), P(d_normals), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
-                                         eng.stream()))
+    if filled is None:
+        _abi.check(eng.lib.kh_cross_sections(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n, P(d_seed),
+                                             P(d_want), P(d_normals), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
+                                             eng.stream()))
+    else:
+        d_begin = t.from_numpy(hole_begin.view(np.int32)).to(eng.device)
+        d_count = t.from_numpy(hole_count.view(np.int32)).to(eng.device)
+        _abi.check(eng.lib.kh_cross_sections_filled(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n,
+                                                    P(d_seed), P(d_want), P(d_normals), P(d_region), P(d_begin), P(d_count),
+                                                    P(d_hole_regions), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
+                                                    eng.stream()))
     if stats is not None:
         after.record(stream)
     area = d_area.cpu().numpy()

@@ -124,7 +124,7 @@ def oversegment(all_labels, skeletons, anisotropy=(1, 1, 1), progress=False, fil
         raise NotImplementedError("oversegment(downsample > 0) needs osteoid's Skeleton.downsample, whose source is not available")
     if fill_holes:
         raise NotImplementedError("oversegment(fill_holes=True): the reference fills every crop on its own and ADDS overlapping "
-                                  "crops, so a filled hole that holds another label sums two numberings")
+                                  "crops, so a filled hole that holds another label sums two numberings (DESIGN.md 7)")
     from .ops import engine
     eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     t = eng.torch
@@ -246,8 +246,8 @@ def _xs_check_arguments(step, smoothing_window, visualize_section_planes, fill_h
     if visualize_section_planes:
         raise NotImplementedError("visualize_section_planes=True paints the planes for microviewer, which is not a dependency here")
     if fill_holes:
-        raise NotImplementedError("cross_sectional_area(fill_holes=True): the reference fills every label's crop on its own; "
-                                  "per-label hole filling of a whole volume is not built (as for oversegment)")
+        raise NotImplementedError("cross_sectional_area(fill_holes=True) keeps raising at this entry point; the sections of filled "
+                                  "labels are cross_sectional_area_filled, which takes the same arguments")
 
 
 def _label_voxel_counts(eng, d_lab, words):
@@ -304,8 +304,9 @@ def _xs_occurrences(skel, an, offset, shape, smoothing_window, step):
     return vox, np.concatenate(occ_vertex), np.concatenate(occ_normal)
 
 
-def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats):
-    """jobs: (skeleton, the device word of its label, the offset of the volume in the skeleton's voxel frame).  The sequential loop
+def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, holes=None):
+    """holes (fill_holes=True): section.hole_tables' (d_region, word_range, d_hole_regions), handed to the launch of every round.
+    jobs: (skeleton, the device word of its label, the offset of the volume in the skeleton's voxel frame).  The sequential loop
     of the reference treats every vertex on its own -- a section depends on (voxel, normal, label) alone -- so its outcome is: a
     branch point is evaluated at every occurrence and ends as the mean; any other vertex is evaluated at its first occurrence when
     its area is 0 (or, repairing, its contact is not), then at the next one for as long as the area comes back 0.  Round 0 launches
@@ -351,8 +352,16 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
         last_of_vertex = np.zeros(sv.size, dtype=bool)
         last_of_vertex[group_end - 1] = True
 
+        if holes is not None:
+            d_region, word_range, d_hole_regions = holes
+            uniq, inverse = np.unique(words, return_inverse=True)
+            ranges = np.array([word_range[int(w)] for w in uniq], dtype=np.uint32).reshape(-1, 2)
+            hole_begin, hole_count = ranges[inverse, 0], ranges[inverse, 1]           # per vertex, as `words`
+
         def launch(which):
-            return section.cross_sections(eng, d_lab, label_bytes, shape, an64, seeds[sv[which]], words[sv[which]], sn[which], stats)[:2]
+            filled = None if holes is None else (d_region, hole_begin[sv[which]], hole_count[sv[which]], d_hole_regions)
+            return section.cross_sections(eng, d_lab, label_bytes, shape, an64, seeds[sv[which]], words[sv[which]], sn[which], stats,
+                                          filled)[:2]
 
         t1 = time.perf_counter()
         open0 = (areas[sv] == 0) | ((contacts[sv] > 0) if repair_contacts else False)
@@ -444,8 +453,29 @@ def cross_sectional_area(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_
     volumes, one skeleton); repair_contacts re-evaluates vertices whose contact is not 0 (after widening the volume).
     A skeleton is skipped when its id is 0, its label does not occur or occupies a single voxel (utility.py:141-154); a bool volume
     assigns every skeleton to label 1.  all_labels: numpy, or a torch tensor on the GPU indexed [x, y, z].
+    fill_holes=True raises NotImplementedError here: cross_sectional_area_filled is that option.
     `progress` and `in_place` are accepted and have no effect."""
     _xs_check_arguments(step, smoothing_window, visualize_section_planes, fill_holes)
+    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, False, multipass, repair_contacts, step, _stats)
+
+
+def cross_sectional_area_filled(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
+                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None):
+    """kimimaro.cross_sectional_area(fill_holes=True): cross_sectional_area, same arguments and outputs, with one substitution.  It
+    takes the sections of filled(L) = L and its holes instead of L (kimimaro/utility.py:152-162 fills every label's
+    crop with fill_voids): a hole of L is a 6-connected piece of the rest of the volume that owns no voxel on a face of the volume,
+    whatever labels it holds, and a vertex inside one is a valid seed.  The volume itself is not changed,
+    and the skip rules look at the label as given.  It costs one region pass over the volume and, while the call lasts,
+    4 bytes per voxel (the region ids) plus 4 bytes per listed hole region on the device; the region pass (Engine.region_graph)
+    allocates another 8 bytes per voxel (union-find parents, representatives), 13 bytes per region (its table) and the pair table
+    (8 bytes x the power of two above 32 slots per region, 4 x that on a retry) and frees them before the first section.
+    cross_sectional_area(fill_holes=False) allocates none of this."""
+    _xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, True, multipass, repair_contacts, step, _stats)
+
+
+def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, multipass, repair_contacts, step, _stats):
+    """the body of cross_sectional_area and cross_sectional_area_filled, after the argument checks"""
     from .ops import engine
     eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
@@ -458,7 +488,11 @@ def cross_sectional_area(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_
     counts = _label_voxel_counts(eng, d_lab, device_label.values())
     jobs = [(s, device_label[L], (0, 0, 0)) for s, L in zip(skels, labels_of)
             if L is not None and L in device_label and counts[device_label[L]] >= 2]       # utility.py:141-154
-    _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats)
+    holes = None
+    if fill_holes and jobs:
+        hole_stats = None if _stats is None else _stats.setdefault("holes", {})
+        holes = section.hole_tables(eng, d_lab, label_bytes, shape, {word for _, word, _ in jobs}, hole_stats)
+    _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats, holes)
     for s in skels:                                                                        # utility.py:551-558
         _add_property(s, XS_PROP)
         _add_property(s, XS_CONTACT_PROP)
