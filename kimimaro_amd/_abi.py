@@ -64,6 +64,11 @@ BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of 
 NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
 
 
+def np_ptr(a):
+    """the address of a numpy array's memory, for the host C functions"""
+    return a.ctypes.data_as(C.c_void_p)
+
+
 def is_pow2_exponent(e):
     """kimimaro/trace.py:343: is_power_of_two(pdrf_exponent) and pdrf_exponent < 2**16 (the repeated-squaring branch).
     The reference's test (trace.py:310-313) evaluates `num & (num - 1)`: an integral FLOAT exponent (16.0, np.float64(4))

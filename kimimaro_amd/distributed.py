@@ -15,6 +15,7 @@ import io
 
 import numpy as np
 
+from .intake import shard_components
 from .skeleton import Skeleton
 
 
@@ -88,5 +89,4 @@ def shard(items, rank, world, weights=None):
     items = list(items)
     if weights is None:
         return items[rank::world]
-    from .intake import shard_components
     return shard_components(items, {i: w for i, w in zip(items, weights)}, rank, world)

@@ -13,11 +13,14 @@ from __future__ import annotations
 import ctypes as C
 import os
 import sys
+import time
 from types import SimpleNamespace
 
 import numpy as np
 
 from . import _abi
+from .holes import resolve_holes
+from .volume import as_3d, ranges
 
 NONE32 = 0xFFFFFFFF
 
@@ -130,6 +133,14 @@ class Engine:
         elif flat.dtype == np.uint64:
             flat = flat.view(np.int64)
         return self.torch.from_numpy(flat).to(self.device)
+
+    def graph_to_device(self, voxel_graph, shape):
+        """a voxel connectivity graph given on the host (cc3d's bit layout; fewer than three axes get trailing ones) -> u32 device
+        volume in Fortran order.  It must have the shape of the labels."""
+        vg = as_3d(voxel_graph)
+        if tuple(vg.shape) != tuple(shape):
+            raise ValueError("voxel_graph must have the shape of the labels")
+        return self.to_device(np.asfortranarray(vg.astype(np.uint32)))
 
     @staticmethod
     def ptr(t):
@@ -273,7 +284,6 @@ class Engine:
         count u32, face u8: host arrays [R + 1]; pairs: host u64, every unordered pair of regions that share a voxel face once, as
         smaller id << 32 | larger id, in no particular order; info: regions, pairs, table_capacity, table_tries, compact_ms).
         mark(name) is called in front of and behind the launches of each pass (Engine.fill_all_holes puts HIP events there)."""
-        import time
         t = self.torch
         sx, sy, sz = shape
         n = sx * sy * sz
@@ -336,8 +346,6 @@ class Engine:
         stats (a dict, optional): region_graph's info, labels, label_value / label_state (the host's verdict per label,
         _abi.HOLES_* bits), filled, resolve_ms, and -- at the price of a synchronisation at the end -- the HIP-event time of every
         pass (regions_ms, table_ms, pairs_ms, apply_ms)."""
-        import time
-        from .intake import resolve_holes
         self.edited(d_lab)
         t = self.torch
         shape = tuple(int(v) for v in shape) + (1,) * (3 - len(shape))
@@ -472,9 +480,7 @@ class Engine:
         t = self.torch
         lib = self.lib
         P = self.ptr
-        m = np.asarray(mask)
-        while m.ndim < 3:
-            m = m[..., np.newaxis]
+        m = as_3d(mask)
         shape = tuple(int(v) for v in m.shape)
         nvox = shape[0] * shape[1] * shape[2]
         cc = np.asfortranarray((m != 0).astype(np.uint32))
@@ -508,12 +514,7 @@ class Engine:
         if voxel_graph is not None:
             # voxel_graph= / voxel_connectivity_graph= of the reference's calls: directions the caller's words do not allow
             # leave the neighbour masks every search and the invalidation work from (kh_apply_voxel_graph)
-            vg = np.asarray(voxel_graph)
-            while vg.ndim < 3:
-                vg = vg[..., np.newaxis]
-            if tuple(int(v) for v in vg.shape) != shape:
-                raise ValueError("voxel_graph must have the shape of the labels")
-            d_graph = self.to_device(np.asfortranarray(vg.astype(np.uint32)))
+            d_graph = self.graph_to_device(voxel_graph, shape)
             d_gate = t.zeros(nvox + 4, dtype=t.uint8, device=self.device)
             _abi.check(lib.kh_apply_voxel_graph(P(d_nbr), P(d_graph), nvox, P(d_gate), st))
         ctx["d_gate"] = d_gate
@@ -701,7 +702,6 @@ class _LabelRun:
     def mark(self, name):
         if self.o.timings is not None:
             self.eng.sync_stream()
-            import time
             self.o.timings.append((name, time.perf_counter()))
 
     def allocate_inputs(self):
@@ -861,12 +861,6 @@ class _LabelRun:
         # gather the used part of the path buffers: build a flat index on the host (small), gather on device
         nverts = part["n_vertices"].astype(np.int64)
         npaths = part["n_paths"].astype(np.int64)
-
-        def ranges(starts, counts):
-            """concatenation of starts[s] + arange(counts[s]) over s, without a Python loop"""
-            total = int(counts.sum())
-            before = np.cumsum(counts) - counts
-            return np.repeat(starts - before, counts) + np.arange(total, dtype=np.int64)
         p_off = self.p.p_off[lo:hi].astype(np.int64)
         d_vidx = t.from_numpy(ranges(p_off, nverts)).to(eng.device)
         d_lidx = t.from_numpy(ranges(p_off, npaths)).to(eng.device)

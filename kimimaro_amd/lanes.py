@@ -19,6 +19,8 @@ import os
 import threading
 import time
 
+from . import intake
+from .engine import Engine
 
 LANE_THREADS = 64     # threads per label of a lane's path loop (Engine.trace_threads): one wave, twelve labels per CU
 LANE_EDF_THREADS = 128   # threads per label of a lane's distance-field searches (Engine.edf_threads)
@@ -107,7 +109,6 @@ class Lanes:
         self.width = int(width)
         if engine_factory is None:
             ensure_hw_queues(self.width)
-            from .engine import Engine
             import torch
 
             def engine_factory():
@@ -280,7 +281,6 @@ def skeletonize_many(volumes, teasar_params=None, lanes=None, width=None, **kwar
     one (called by the lane that takes the job, so loading overlaps tracing).  Yields (index, {label: Skeleton}) in order.
     `lanes`: a Lanes object to reuse; else `width` lanes are made (default: lanes_for() on the first volume's shape).
     The other keyword arguments are those of kimimaro_amd.skeletonize."""
-    from . import intake
     n = len(volumes)
     if n == 0:
         return
@@ -345,7 +345,6 @@ def _lane_main(conn, device, setup, setup_args, index, engine_factory):
     import traceback
     try:
         if engine_factory is None:
-            from .engine import Engine
             eng = Engine(device)
             if "KH_TRACE_THREADS" not in os.environ:
                 eng.trace_threads = LANE_THREADS

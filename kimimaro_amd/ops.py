@@ -6,8 +6,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _abi
+from . import _abi, feature, points, section
 from .engine import Engine
+from .volume import as_3d, coords_of, linear_index
 
 _engine = None
 
@@ -29,21 +30,14 @@ def edt(labels, anisotropy=(1, 1, 1), black_border=False, parallel=1, voxel_grap
         lab = lab.view(np.uint8)
     if lab.dtype.kind not in "ui" or lab.dtype.itemsize > 4:
         lab = lab.astype(np.uint32)
-    while lab.ndim < 3:
-        lab = lab[..., np.newaxis]
-    lab = np.asfortranarray(lab)
+    lab = np.asfortranarray(as_3d(lab))
     an = list(anisotropy) + [1.0] * (3 - len(anisotropy))
     if voxel_graph is not None:
         # edt.edt(voxel_graph=): walls between voxels (kh_edt_graph_cells / kh_edt_graph_sample; the package is absent from the
         # reference tree: PARITY UNPINNED, include/kimi_hip.h)
         if ndim < 3 and black_border:
             raise NotImplementedError("edt(voxel_graph=, black_border=True) on fewer than three axes")
-        vg = np.asarray(voxel_graph)
-        while vg.ndim < 3:
-            vg = vg[..., np.newaxis]
-        if tuple(vg.shape) != tuple(lab.shape):
-            raise ValueError("voxel_graph must have the shape of the labels")
-        d_graph = eng.to_device(np.asfortranarray(vg.astype(np.uint32)))
+        d_graph = eng.graph_to_device(voxel_graph, lab.shape)
         out = eng.edt_graph(eng.to_device(lab), lab.dtype.itemsize, d_graph, lab.shape, an, black_border)
         return out.cpu().numpy().reshape(lab.shape, order="F").reshape(shape0, order="F")
     out = eng.edt(eng.to_device(lab), lab.dtype.itemsize, lab.shape, an, black_border, ndim=ndim)
@@ -120,19 +114,8 @@ def roll_invalidation_ball_inside_component(labels, DBF, scale, const, anisotrop
 # own vectors can be fed to the HIP implementation of every step.
 
 def _f3(a, dtype=None):
-    a = np.asarray(a)
-    while a.ndim < 3:
-        a = a[..., np.newaxis]
+    a = as_3d(a)
     return np.asfortranarray(a if dtype is None else a.astype(dtype, copy=False))
-
-
-def _loc(pt, shape):
-    return int(pt[0]) + shape[0] * (int(pt[1]) + shape[1] * int(pt[2]))
-
-
-def _pts(locs, shape):
-    locs = np.asarray(locs, dtype=np.int64)
-    return np.stack([locs % shape[0], (locs // shape[0]) % shape[1], locs // (shape[0] * shape[1])], axis=1)
 
 
 def zero2inf(field):
@@ -200,7 +183,6 @@ def _edf_many_sources(labels, sources, anisotropy, return_max_location, return_f
     """euclidean_distance_field from several sources at once, as kimimaro/utility.py:613-617 calls it: the whole-volume relaxation
     of kimimaro_amd.feature (csrc/feature.hip) on the mask; feature_map = 1-based number of the nearest source (the smallest among
     equally far ones), 0 where the field is +inf."""
-    from . import feature
     eng = engine()
     lab = _f3(labels)
     shape = tuple(int(v) for v in lab.shape)
@@ -219,7 +201,7 @@ def _edf_many_sources(labels, sources, anisotropy, return_max_location, return_f
         t = eng.torch
         reach = t.where(t.isfinite(d_dist), d_dist, t.full_like(d_dist, -1.0))
         loc = int(t.nonzero(reach == reach.max())[0].item())          # ties -> smallest linear index, like kh_edf_batch
-        out.append(tuple(int(v) for v in _pts([loc], shape)[0]))
+        out.append(tuple(int(v) for v in coords_of([loc], shape)[0]))
     if return_feature_map:
         fm = d_feat.cpu().numpy().view(np.uint32)
         fm[fm == _abi.NO_FEATURE] = 0
@@ -247,7 +229,7 @@ def euclidean_distance_field(labels, source, anisotropy=(1, 1, 1), free_space_ra
     shape = ctx["shape"]
     t = eng.torch
     task = ctx["task"]
-    task["root"] = _loc(source, shape)
+    task["root"] = linear_index(source, shape)
     task["fsr"] = np.float32(free_space_radius)
     d_task = t.from_numpy(task.view(np.uint8).reshape(-1).copy()).to(eng.device)
     d_field = t.full((ctx["nvox"] + 4,), float("inf"), dtype=t.float32, device=eng.device)   # (+ padding: the searches read rows of three words)
@@ -259,7 +241,7 @@ def euclidean_distance_field(labels, source, anisotropy=(1, 1, 1), free_space_ra
     if not return_max_location:
         return out
     done = d_task.cpu().numpy().view(_abi.LABEL_T)
-    return out, tuple(int(v) for v in _pts([int(done["max_loc"][0])], shape)[0])
+    return out, tuple(int(v) for v in coords_of([int(done["max_loc"][0])], shape)[0])
 
 
 class _Search:
@@ -291,14 +273,14 @@ class _Search:
         if status:
             raise _abi.KimiHipError("kh_path_search: %s" % _abi.describe_status(status))
         n = int(d_n.item())
-        return _pts(d_path[:n].cpu().numpy().view(np.uint32), self.shape)
+        return coords_of(d_path[:n].cpu().numpy().view(np.uint32), self.shape)
 
 
 def railroad(field, source, voxel_graph=None):
     """dijkstra3d.railroad(field, source) as called at kimimaro/trace.py:240-242: the path from `source` to the nearest
     zero-weight voxel, rail end first, as an (n, 3) array."""
     s = _Search(field, voxel_graph)
-    return s.run(0, _loc(source, s.shape))
+    return s.run(0, linear_index(source, s.shape))
 
 
 def parental_field(field, source, voxel_graph=None):
@@ -310,7 +292,7 @@ def parental_field(field, source, voxel_graph=None):
     sx, sy, sz = s.shape
     d_par = eng.empty(sx * sy * sz, t.int32)
     _abi.check(eng.lib.kh_parental_field(P(ctx["d_task"]), P(ctx["d_lists"]), P(ctx["d_nbr"]), sx, sy, sz, P(s.d_field), P(s.d_dist),
-                                         P(ctx["d_qstate"]), P(ctx["d_queues"]), _loc(source, s.shape), P(d_par), int(s.graph),
+                                         P(ctx["d_qstate"]), P(ctx["d_queues"]), linear_index(source, s.shape), P(d_par), int(s.graph),
                                          eng.stream()))
     status = int(ctx["d_task"].cpu().numpy().view(_abi.LABEL_T)["status"][0])
     if status:
@@ -329,11 +311,11 @@ def path_from_parents(parents, target):
     cap = par.size
     d_path = eng.empty(cap, t.int32)
     d_n = t.zeros(1, dtype=t.int32, device=eng.device)
-    _abi.check(eng.lib.kh_path_from_parents(P(d_par), par.size, _loc(target, shape), P(d_path), cap, P(d_n), eng.stream()))
+    _abi.check(eng.lib.kh_path_from_parents(P(d_par), par.size, linear_index(target, shape), P(d_path), cap, P(d_n), eng.stream()))
     n = int(d_n.item())
     if n == 0:
         raise _abi.KimiHipError("kh_path_from_parents: the parents of the target do not lead to a voxel without a parent")
-    return _pts(d_path[:n].cpu().numpy().view(np.uint32), shape)
+    return coords_of(d_path[:n].cpu().numpy().view(np.uint32), shape)
 
 
 def dijkstra(field, source, target, voxel_graph=None):
@@ -342,9 +324,9 @@ def dijkstra(field, source, target, voxel_graph=None):
     search as parental_field + path_from_parents (one weighted Dijkstra from the source, predecessor walk from the
     target); ties between equally cheap paths follow the canonical predecessor rule of DESIGN.md 3.3."""
     s = _Search(field, voxel_graph)
-    src = _loc(source, s.shape)
+    src = linear_index(source, s.shape)
     s.run(1, src)                                   # (the predecessor WALK crosses float-absorption plateaus, which a
-    return s.run(2, src, _loc(target, s.shape))     # parents array cannot express: DESIGN.md 3.3)
+    return s.run(2, src, linear_index(target, s.shape))     # parents array cannot express: DESIGN.md 3.3)
 
 
 def extract_edges_from_binary_image(binimg, connectivity=26):
@@ -353,7 +335,6 @@ def extract_edges_from_binary_image(binimg, connectivity=26):
     axis, 18: also across a face diagonal, 26: also across a corner) and the voxels that lie on such a pair.  The reference numbers
     them in the iteration order of an unordered_set; here vertices come by ascending Fortran index, edges as (a, b), a < b, sorted
     by a, then b.  binimg: numpy, or a torch tensor on the GPU; bool or any integer dtype."""
-    from . import points
     img = points.check_binary_image(binimg)          # TypeError / DimensionError before anything touches the GPU
     eng = engine()
     d_img, shape = points.device_binary_image(eng, img)
@@ -372,7 +353,7 @@ def first_label(labels):
     loc = int(d_out.cpu().numpy().view(np.uint64)[0])
     if loc == 0xFFFFFFFFFFFFFFFF:
         return None
-    return tuple(int(v) for v in _pts([loc], lab.shape)[0])
+    return tuple(int(v) for v in coords_of([loc], lab.shape)[0])
 
 
 def find_target(labels, PDRF):
@@ -419,7 +400,7 @@ class CachedTargetFinder:
         key = int(d_out.cpu().numpy().view(np.uint64)[0])
         if key == 0:
             return None
-        return tuple(int(v) for v in _pts([key & 0xFFFFFFFF], self.shape)[0])
+        return tuple(int(v) for v in coords_of([key & 0xFFFFFFFF], self.shape)[0])
 
 
 def cross_sectional_area(binimg, pos, normal, anisotropy=(1, 1, 1), return_contact=False):
@@ -429,7 +410,6 @@ def cross_sectional_area(binimg, pos, normal, anisotropy=(1, 1, 1), return_conta
     return_contact also the bits of the volume faces that piece touches (1, 2: x low, high; 4, 8: y; 16, 32: z).  0 for a position
     on the background or outside the image and for a zero or non-finite normal.  `pos` is rounded to a voxel.
     binimg: numpy, or a torch tensor on the GPU; bool or any integer dtype, foreground = non-zero."""
-    from . import points, section
     img = points.check_binary_image(binimg)          # TypeError / DimensionError before anything touches the GPU
     eng = engine()
     d_img, shape = points.device_binary_image(eng, img)

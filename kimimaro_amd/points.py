@@ -6,6 +6,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
+from .volume import DimensionError, format_labels
 
 NONE64 = 0xFFFFFFFFFFFFFFFF       # the "none" word of kh_nearest_label_voxels
 MAX_EDGES = 2 ** 31
@@ -81,7 +82,6 @@ def binary_edges(eng, d_img, shape, connectivity=26):
 def check_binary_image(image):
     """The checks that need no GPU: the dtype (bool or integers) and the dimensions (a fourth non-trivial axis is a DimensionError).
     numpy -> the u8 array of 0 / 1 with three axes, Fortran ordered; a torch tensor comes back with at most three axes."""
-    from .intake import DimensionError, format_labels
     if hasattr(image, "permute") and hasattr(image, "device"):          # a torch tensor
         if image.dtype.is_floating_point or image.dtype.is_complex:
             raise TypeError("the image must be bool or integers")

@@ -3,9 +3,12 @@ label volume resident in HBM, one launch.  kimimaro_amd.utility.cross_sectional_
 the callers.  The library allocates nothing: the scratch (visited bitmaps and queue spill of the concurrent waves) is sized here."""
 from __future__ import annotations
 
+import time
+
 import numpy as np
 
 from . import _abi
+from .holes import enclosed_regions
 
 OUTSIDE = 0xFFFFFFFF               # the seed word of a vertex outside the volume (never a voxel: fewer than 2^32 - 1 voxels)
 MAX_WAVES = 2048                   # 256 CUs x 8 resident waves of the kernel
@@ -27,8 +30,6 @@ def hole_tables(eng, d_lab, label_bytes, shape, words, stats=None):
     (kh_host_enclosed_regions).  Returns (d_region: u32 region id per voxel, resident; word_range: {word: (begin, count)} into
     d_hole_regions: the lists, resident, never empty so that it has an address).  Resident: 4 bytes per voxel plus the lists.
     stats (a dict) receives region_graph's info, enclosed_ms (the host search), csr_regions and labels_with_holes."""
-    import time
-    from .intake import enclosed_regions
     t = eng.torch
     marks = []
 

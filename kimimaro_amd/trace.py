@@ -5,10 +5,19 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import ops
+from .assemble import paths_of
 from .engine import Engine, NONE32
 from .plan import LabelSet
-from .intake import TRACE_DEFAULTS, paths_of
 from .skeleton import Skeleton
+from .volume import as_3d, linear_index
+
+# kimimaro/trace.py:38-43 -- the defaults trace() falls back to for keys missing from teasar_params
+TRACE_DEFAULTS = {
+    "scale": 10, "const": 10, "soma_detection_threshold": 1100, "soma_acceptance_threshold": 4000,
+    "pdrf_scale": 5000, "pdrf_exponent": 16, "soma_invalidation_scale": 0.5, "soma_invalidation_const": 0,
+    "max_paths": None,
+}
 
 
 def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
@@ -17,10 +26,7 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
           fix_branching=True, manual_targets_before=None, manual_targets_after=None, root=None,
           max_paths=None, voxel_graph=None, return_paths=False, _engine=None, _return_raw=False):
     eng = _engine or Engine()
-    labels = np.asarray(labels)
-    while labels.ndim < 3:
-        labels = labels[..., np.newaxis]
-        DBF = np.asarray(DBF)[..., np.newaxis]
+    labels, DBF = as_3d(labels), as_3d(DBF)
     shape = labels.shape
     cc = np.asfortranarray((labels != 0).astype(np.uint32))
     dbf = np.asfortranarray(DBF, dtype=np.float32)
@@ -29,7 +35,7 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
     stats = eng.label_stats(d_cc, 4, d_dbf, shape, 1)
     if stats.counts[1] == 0:
         return [] if return_paths else Skeleton()
-    loc = lambda p: int(p[0]) + shape[0] * (int(p[1]) + shape[1] * int(p[2]))
+    loc = lambda p: linear_index(p, shape)
     mtb = [loc(p) for p in (manual_targets_before or [])]
     mta = [loc(p) for p in (manual_targets_after or [])]
     dmax = np.float32(stats.dbf_max[1])
@@ -37,12 +43,7 @@ def trace(labels, DBF, scale=10, const=10, anisotropy=(1, 1, 1),
     d_graph = None
     if voxel_graph is not None:
         # trace.py:139-145,155,167,240-242,257: the graph goes to every dijkstra3d search and to the invalidation
-        vg = np.asarray(voxel_graph)
-        while vg.ndim < 3:
-            vg = vg[..., np.newaxis]
-        if tuple(vg.shape) != tuple(shape):
-            raise ValueError("voxel_graph must have the shape of the labels")
-        d_graph = eng.to_device(np.asfortranarray(vg.astype(np.uint32)))
+        d_graph = eng.graph_to_device(voxel_graph, shape)
     if dmax > soma_detection_threshold:  # kimimaro/trace.py:108-119
         # fill_voids.fill (kh_fill_voids, row f3) + crop re-EDT, both on the GPU
         d_filled, nfilled = eng.fill_voids((d_cc != 0).to(eng.torch.uint8), shape)
@@ -97,7 +98,6 @@ def point_to_point(binary_img, start, end, anisotropy=(1, 1, 1), pdrf_scale=1000
     image -- EDT with black_border, DAF from `start`, PDRF, then the cheapest path end -> start over the PDRF
     (dijkstra3d.dijkstra); radii are the (zero2inf'ed) DBF at the vertices, as in the reference.  Every step is the HIP
     kernel behind the function-level mirror of the module the reference calls (kimimaro_amd.ops)."""
-    from . import ops
     img = np.asfortranarray(binary_img)
     DBF = ops.edt(img, anisotropy=anisotropy, black_border=True)
     dbf_max = np.max(DBF)

@@ -13,9 +13,9 @@ import time
 
 import numpy as np
 
-from . import _abi, feature, section
-from .intake import format_labels
+from . import _abi, feature, ops, points, section
 from .skeleton import Skeleton
+from .volume import _device_labels
 
 SEGMENTS_ATTRIBUTE = {"id": "segments", "data_type": "uint64", "num_components": 1}    # utility.py:583-587
 XS_PROP = {"id": "cross_sectional_area", "data_type": "float32", "num_components": 1}                # utility.py:23-27
@@ -27,8 +27,7 @@ def extract_skeleton_from_binary_image(image):
     thinned already into a Skeleton -- every foreground voxel with a foreground 26-neighbour is a vertex, every such pair an edge
     (kimimaro_amd.ops.extract_edges_from_binary_image: the canonical numbering of DESIGN.md 3.11).  image: numpy, or a torch tensor
     on the GPU indexed [x, y(, z)]; bool or integers, foreground = non-zero."""
-    from .ops import extract_edges_from_binary_image
-    verts, edges = extract_edges_from_binary_image(image)
+    verts, edges = ops.extract_edges_from_binary_image(image)
     return Skeleton(verts, edges)
 
 
@@ -39,38 +38,6 @@ def _skeleton_list(skeletons):
     if isinstance(skeletons, dict):
         return list(skeletons.values())
     return list(skeletons)
-
-
-def _device_labels(eng, all_labels):
-    """-> (1-D device tensor in Fortran order, bytes per label, bool volume?, (sx, sy, sz), shape to return, (smallest, largest) label
-    the dtype can hold).  numpy input goes through format_labels like skeletonize's; a torch tensor on the engine's device, indexed
-    [x, y, z], is taken as it is (a view that is Fortran ordered already -- a contiguous (z, y, x) tensor permuted -- is not copied)."""
-    t = eng.torch
-    if isinstance(all_labels, t.Tensor):
-        if all_labels.device != eng.device:
-            raise ValueError("a label tensor must live on the engine's device (%s)" % eng.device)
-        if all_labels.ndim > 3:
-            raise ValueError("a label tensor has at most three axes")
-        if all_labels.dtype.is_floating_point or all_labels.dtype.is_complex:
-            raise TypeError("labels must be integers or bool")
-        shape0 = tuple(int(v) for v in all_labels.shape)
-        vol = all_labels
-        while vol.ndim < 3:
-            vol = vol.unsqueeze(-1)
-        shape = tuple(int(v) for v in vol.shape)
-        is_bool = vol.dtype == t.bool
-        flat = vol.permute(2, 1, 0).contiguous().reshape(-1)
-        size = flat.element_size()
-        span = (-(1 << (8 * size - 1)), (1 << (8 * size - 1)) - 1) if vol.dtype.is_signed else (0, (1 << (8 * size)) - 1)
-        return flat.view({1: t.uint8, 2: t.int16, 4: t.int32, 8: t.int64}[size]), size, is_bool, shape, shape0, span
-    arr = np.asarray(all_labels)
-    if arr.dtype != np.bool_ and arr.dtype.kind not in "ui":
-        raise TypeError("labels must be integers or bool")
-    is_bool = arr.dtype == np.bool_
-    vol = format_labels(arr, in_place=True)          # (no copy of a Fortran-ordered volume: nothing here writes to it)
-    info = np.iinfo(vol.dtype)
-    return (eng.to_device(vol.view("u%d" % vol.dtype.itemsize)), vol.dtype.itemsize, is_bool, tuple(int(v) for v in vol.shape),
-            arr.shape, (int(info.min), int(info.max)))
 
 
 def _narrow_labels(eng, d_flat, itemsize, span, wanted):
@@ -125,8 +92,7 @@ def oversegment(all_labels, skeletons, anisotropy=(1, 1, 1), progress=False, fil
     if fill_holes:
         raise NotImplementedError("oversegment(fill_holes=True): the reference fills every crop on its own and ADDS overlapping "
                                   "crops, so a filled hole that holds another label sums two numberings (DESIGN.md 7)")
-    from .ops import engine
-    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     t = eng.torch
     an = np.array(anisotropy, dtype=np.float32).reshape(-1)
     if an.shape != (3,) or not np.all(np.isfinite(an)) or not np.all(an > 0):
@@ -422,10 +388,8 @@ def cross_sectional_area_single(binimg, skel, roi=None, anisotropy=(1, 1, 1), sm
     voxel frame -- anything with a `.minpt`, or three numbers -- subtracted from the vertices.  Everything else as
     cross_sectional_area.  The skeleton is changed in place and returned."""
     _xs_check_arguments(step, smoothing_window, visualize_section_planes)
-    from . import points
-    from .ops import engine
     img = points.check_binary_image(binimg)
-    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
     d_img, shape = points.device_binary_image(eng, img)
     offset = np.zeros(3, dtype=np.int64) if roi is None else np.asarray(getattr(roi, "minpt", roi), dtype=np.int64).reshape(3)
@@ -476,8 +440,7 @@ def cross_sectional_area_filled(all_labels, skeletons, anisotropy=(1, 1, 1), smo
 
 def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, multipass, repair_contacts, step, _stats):
     """the body of cross_sectional_area and cross_sectional_area_filled, after the argument checks"""
-    from .ops import engine
-    eng = engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
     skels = _skeleton_list(skeletons)
     d_flat, itemsize, is_bool, shape, _, span = _device_labels(eng, all_labels)

@@ -152,3 +152,37 @@ def test_trace_soma_with_voids_and_graph_runs_the_graph_transform(eng):
     assert len(got) == len(want) and len(want) > 0
     for x, y in zip(got, want):
         np.testing.assert_array_equal(np.asarray(x), np.asarray(y))
+
+
+def _small_mask():
+    m = np.ones((8, 6, 4), dtype=np.uint8, order="F")
+    m[3, 2:, :] = 0                      # (a wall with a gap: background, and a detour for the searches)
+    return m
+
+
+@pytest.mark.parametrize("entry", ["skeletonize", "edt", "euclidean_distance_field", "trace"])
+def test_voxel_graph_of_another_shape_is_a_value_error(eng, entry):
+    """every entry point that takes a host voxel graph checks it against the labels' shape, with one message"""
+    import kimimaro_amd
+    from kimimaro_amd import ops
+    from kimimaro_amd.trace import trace
+    m = _small_mask()
+    g = np.full((8, 6, 3), 0x3FFFFFF, dtype=np.uint32, order="F")
+    calls = {"skeletonize": lambda: kimimaro_amd.skeletonize(m, dust_threshold=0, progress=False, voxel_graph=g, _engine=eng),
+             "edt": lambda: ops.edt(m, voxel_graph=g),
+             "euclidean_distance_field": lambda: ops.euclidean_distance_field(m, (0, 0, 0), voxel_graph=g),
+             "trace": lambda: trace(m, np.ones(m.shape, dtype=np.float32, order="F"), voxel_graph=g, _engine=eng)}
+    with pytest.raises(ValueError) as err:
+        calls[entry]()
+    assert str(err.value) == "voxel_graph must have the shape of the labels"
+
+
+def test_full_graph_on_a_2d_mask_is_the_field_without_a_graph():
+    """a 2-D mask takes a 2-D graph (both get their third axis), and a graph with all 26 direction bits set forbids nothing"""
+    from kimimaro_amd import ops
+    m = _small_mask()[:, :, 0]
+    g = np.full(m.shape, 0x3FFFFFF, dtype=np.uint32, order="F")
+    want = ops.euclidean_distance_field(m, (0, 0, 0), anisotropy=(2, 3, 5))
+    got = ops.euclidean_distance_field(m, (0, 0, 0), anisotropy=(2, 3, 5), voxel_graph=g)
+    assert got.shape == (8, 6) and np.isfinite(want[7, 5]) and np.isinf(want[3, 4])
+    np.testing.assert_array_equal(got, want)
