@@ -586,6 +586,40 @@ int64_t kh_host_merge_components(int64_t nlabels, const int64_t* part_of_label, 
                                  const float* verts, const float* radii, const uint32_t* edges, int64_t sy, int64_t sz,
                                  float ax, float ay, float az, float* out_verts, float* out_radii, uint32_t* out_edges);
 
+/* ---- row f4 on the device: the nearest vertex pairs between the parts of skeleton groups ------------------
+ * replaces: the cKDTree queries of kimimaro/post.py:89-218 (join_close_components), which are repeated after every merge; here
+ * one table of raw nearest pairs between all ORIGINAL parts determines the whole merge sequence (kh_host_join_plan below).
+ * Parts: the components of the skeletons of a group, consolidated, the empty ones dropped; vertex k of a part is its row k.
+ * Device inputs: xyz f32 [V,3], the vertices of all parts back to back; part_start u32 [P+1]; part_box f32 [P,6] = (min x, y, z,
+ * max x, y, z) of every part; group_start u32 [G+1], indexing parts; bound2 f64 [G]; rec_start i64 [G+1] with
+ * rec_start[g+1] - rec_start[g] = n_g * n_g for the n_g parts of group g, rec_start[G] = nrecords (at most 2^26: 1 GiB of tables).
+ * Outputs, every cell written: rec_d2 [nrecords] (the bits of an f64) and rec_idx [nrecords,2] = (kt, kq); the cell of tree part
+ * t and query part q of group g, both local to the group, is rec_start[g] + t * n_g + q.
+ * Record R[t][q], t != q: the lexicographic minimum of (d2, kq, kt) over the vertices kq of q and kt of t, where
+ * d2 = ((dx*dx + dy*dy) + dz*dz), dx = (double)xq - (double)xt, every operation rounded in f64, no FMA.  It is "none" exactly when
+ * that minimal d2 >= bound2[g] (+inf allowed: nothing is none), stored as d2 = the bits of +inf and both indices 0xFFFFFFFF; so is
+ * the diagonal.  No record crosses groups.  Pairs whose boxes are at least the bound apart are not visited.  Asynchronous on
+ * `stream`; the library allocates nothing.                                                                                     */
+int kh_part_gaps(const float* xyz, const uint32_t* part_start, const float* part_box, const uint32_t* group_start,
+                 const double* bound2, const int64_t* rec_start, int64_t ngroups, int64_t nrecords, uint64_t* rec_d2,
+                 uint32_t* rec_idx, void* stream);
+
+/* ---- row f4 (host side, no GPU): the merge plan of join_close_components (kimimaro/post.py:89-218) for ONE group, reading only
+ * the table of its nparts parts: rec_d2 [nparts*nparts], rec_idx [nparts*nparts,2] as above; part_size [nparts]; radii = the
+ * parts' vertex radii back to back; radius = the value the search ends up with (with restrict_by_radius: twice the largest
+ * vertex radius, computed by the caller, who derived bound2 = (radius + 0.000001)^2 from it).
+ * A cluster is an ordered list of (original part, vertex offset); at first every part is one.  The gap of cluster A as tree and
+ * cluster B as query is the lexicographic minimum of (d2, kq + offset_B, kt + offset_A) over the records R[a][b] of their members
+ * that are not none; d = sqrt(d2); with restrict_by_radius a d above the float32 sum of the two vertices' radii counts as
+ * infinite; the key is (float)d.  Repeatedly: the smallest (key, i, j), i < j in the current numbering -- the fused cluster
+ * first, the rest in their previous order, the earlier cluster being the tree -- is merged (A's members, then B's) unless the key
+ * is not finite or (double)key > radius, which ends the plan.  Each merge writes one edge (tree vertex, query vertex) in the
+ * numbering of the concatenated ORIGINAL parts; edges has room for (nparts - 1) * 2 entries.
+ * Returns the number of edges; -1 for a bad argument (null pointer, nparts < 0, more than 2^32 - 1 vertices, an index outside
+ * its part in a record that is not none), -2 on allocation failure.                                                            */
+int64_t kh_host_join_plan(int64_t nparts, const uint32_t* part_size, const uint64_t* rec_d2, const uint32_t* rec_idx,
+                          const float* radii, double radius, int restrict_by_radius, uint32_t* edges);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ SYMBOLS = [
     "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
     "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
     "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
+    "kh_part_gaps", "kh_host_join_plan",
 ]
 
 
@@ -179,11 +180,14 @@ def lib():
     L.kh_host_resolve_holes.restype = i64
     L.kh_host_enclosed_regions.argtypes = [i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]
     L.kh_host_enclosed_regions.restype = i64
+    L.kh_part_gaps.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
+    L.kh_host_join_plan.argtypes = [i64, vp, vp, vp, vp, f64, ci, vp]
+    L.kh_host_join_plan.restype = i64
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",
                         "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths",
-                        "kh_host_resolve_holes", "kh_host_enclosed_regions"):
+                        "kh_host_resolve_holes", "kh_host_enclosed_regions", "kh_host_join_plan"):
             getattr(L, name).restype = ci
     _lib = L
     return L

@@ -417,3 +417,15 @@ def cross_sectional_area(binimg, pos, normal, anisotropy=(1, 1, 1), return_conta
     n = np.asarray(normal, dtype=np.float64).reshape(1, 3)
     area, contact, _ = section.cross_sections(eng, d_img, 1, shape, anisotropy, section.seed_index(vox, shape), np.ones(1, np.uint32), n)
     return (float(area[0]), int(contact[0])) if return_contact else float(area[0])
+
+
+def component_gaps(parts, bound=np.inf):
+    """The table of nearest vertex pairs join_close_components_many works from (kh_part_gaps), for the parts of ONE
+    group: Skeletons or (k, 3) vertex arrays, none of them empty.  Returns (d2 f64 [n, n], idx u32 [n, n, 2]): row = tree part,
+    column = query part, d2 = the smallest squared distance in f64, idx = (tree vertex, query vertex) of the lexicographically
+    smallest (d2, query vertex, tree vertex).  A pair whose d2 >= bound * bound has no record: d2 = +inf, both indices 0xFFFFFFFF;
+    so has the diagonal."""
+    verts = [np.asarray(getattr(p, "vertices", p), dtype=np.float32).reshape(-1, 3) for p in parts]
+    eng = engine()
+    bound = float(bound)
+    return points.part_gaps(eng, [verts], [bound * bound])[0]

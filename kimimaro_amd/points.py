@@ -1,7 +1,10 @@
-"""Device plumbing of the two point queries (csrc/points.hip): the voxel of a label nearest to a centroid
-(kimimaro_amd.intake.synapses_to_targets) and the edges of a binary image (kimimaro_amd.ops.extract_edges_from_binary_image).
-Everything works on whole-volume arrays resident in HBM; the library allocates nothing, the scratch is sized here."""
+"""Device plumbing of the point queries: the voxel of a label nearest to a centroid (kimimaro_amd.intake.synapses_to_targets) and
+the edges of a binary image (kimimaro_amd.ops.extract_edges_from_binary_image), both csrc/points.hip, DESIGN.md 3.11, on
+whole-volume arrays resident in HBM; and the nearest vertex pairs between the parts of skeleton groups (part_gaps: csrc/join.hip,
+DESIGN.md 3.14; kimimaro_amd.post.join_close_components_many).  The library allocates nothing, the scratch is sized here."""
 from __future__ import annotations
+
+import time
 
 import numpy as np
 
@@ -10,6 +13,8 @@ from .volume import DimensionError, format_labels
 
 NONE64 = 0xFFFFFFFFFFFFFFFF       # the "none" word of kh_nearest_label_voxels
 MAX_EDGES = 2 ** 31
+GAP_MAX_RECORDS = 1 << 26         # records (16 bytes each) of one kh_part_gaps call: 1 GiB of tables
+GAP_MAX_PARTS = 8192              # ... which is one group of this many parts
 
 
 def connectivity_directions(connectivity):
@@ -107,3 +112,76 @@ def device_binary_image(eng, image):
     while vol.ndim < 3:
         vol = vol.unsqueeze(-1)
     return (vol != 0).permute(2, 1, 0).contiguous().reshape(-1).to(t.uint8), tuple(int(v) for v in vol.shape)
+
+
+def gap_launches(counts):
+    """counts: parts per group -> the groups of every kh_part_gaps call, in order, so that the tables of one call (counts[g]^2 records
+    per group) stay within GAP_MAX_RECORDS; a single group beyond that is a ValueError"""
+    launches, used = [], 0
+    for g, n in enumerate(counts):
+        n = int(n)
+        if n > GAP_MAX_PARTS:
+            raise ValueError("a group has %d parts: more than %d, whose table of nearest pairs exceeds 1 GiB" % (n, GAP_MAX_PARTS))
+        if not launches or used + n * n > GAP_MAX_RECORDS:
+            launches.append([])
+            used = 0
+        launches[-1].append(g)
+        used += n * n
+    return launches
+
+
+def part_gaps(eng, groups, bound2, timings=None):
+    """groups: per group the list of its parts' vertices (f32 [k, 3], k >= 1); bound2: per group the f64 bound on d2 (+inf: none).
+    Returns per group (d2 f64 [n, n], idx u32 [n, n, 2]): the records of kh_part_gaps (include/kimi_hip.h), row = tree part, column =
+    query part, idx = (kt, kq); "none" is d2 = +inf and both indices 0xFFFFFFFF.  One call of the kernel for all groups, or a few
+    under gap_launches.  timings (a dict): gets kernel_ms (HIP events around the calls) and copy_s (the tables' way to the host)."""
+    t, P = eng.torch, eng.ptr
+    out = [None] * len(groups)
+    kernel_ms, copy_s = 0.0, 0.0
+    for launch in gap_launches([len(g) for g in groups]):
+        parts = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3) for g in launch for p in groups[g]]
+        counts = np.array([len(groups[g]) for g in launch], dtype=np.int64)
+        rec_start = np.concatenate([[0], np.cumsum(counts * counts)]).astype(np.int64)
+        nrec = int(rec_start[-1])
+        if nrec == 0:
+            for g in launch:
+                out[g] = np.zeros((0, 0), dtype=np.float64), np.zeros((0, 0, 2), dtype=np.uint32)
+            continue
+        sizes = np.array([p.shape[0] for p in parts], dtype=np.int64)
+        if sizes.min() < 1:
+            raise ValueError("a part without vertices")
+        if int(sizes.sum()) >= 2 ** 32:
+            raise ValueError("the parts of one call hold %d vertices, more than 2^32 - 1" % int(sizes.sum()))
+        part_start = np.concatenate([[0], np.cumsum(sizes)])
+        xyz = np.concatenate(parts, axis=0)
+        box = np.concatenate([np.minimum.reduceat(xyz, part_start[:-1], axis=0), np.maximum.reduceat(xyz, part_start[:-1], axis=0)], axis=1)
+        group_start = np.concatenate([[0], np.cumsum(counts)])
+        d_xyz = t.from_numpy(xyz).to(eng.device)
+        d_pstart = t.from_numpy(part_start.astype(np.uint32).view(np.int32)).to(eng.device)
+        d_box = t.from_numpy(np.ascontiguousarray(box, dtype=np.float32)).to(eng.device)
+        d_gstart = t.from_numpy(group_start.astype(np.uint32).view(np.int32)).to(eng.device)
+        d_bound = t.from_numpy(np.array([bound2[g] for g in launch], dtype=np.float64)).to(eng.device)
+        d_rstart = t.from_numpy(rec_start).to(eng.device)
+        d_d2 = eng.empty(nrec, t.int64)
+        d_idx = eng.empty(2 * nrec, t.int32)
+        if timings is not None:
+            begin, end = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            begin.record()
+        _abi.check(eng.lib.kh_part_gaps(P(d_xyz), P(d_pstart), P(d_box), P(d_gstart), P(d_bound), P(d_rstart), len(launch), nrec,
+                                        P(d_d2), P(d_idx), eng.stream()))
+        if timings is not None:
+            end.record()
+            end.synchronize()
+            kernel_ms += begin.elapsed_time(end)
+            t0 = time.perf_counter()
+        d2 = d_d2.cpu().numpy().view(np.float64)
+        idx = d_idx.cpu().numpy().view(np.uint32)
+        if timings is not None:
+            copy_s += time.perf_counter() - t0
+        for k, g in enumerate(launch):
+            n = int(counts[k])
+            out[g] = (d2[rec_start[k]:rec_start[k + 1]].reshape(n, n), idx[2 * rec_start[k]:2 * rec_start[k + 1]].reshape(n, n, 2))
+    if timings is not None:
+        timings["kernel_ms"] = timings.get("kernel_ms", 0.0) + kernel_ms
+        timings["copy_s"] = timings.get("copy_s", 0.0) + copy_s
+    return out

@@ -4,8 +4,13 @@
     join_close_components(skeletons, radius=inf, restrict_by_radius)    kimimaro/post.py:89-218
     remove_dust / remove_loops / remove_ticks                            kimimaro/post.py:222-260, 436-563
 
-Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so is this; nothing
-in it touches the GPU path.  Written from the behaviour of the reference, including the parts that are visible in its
+    join_close_components_many(groups, radius=inf, restrict_by_radius)  the join of many groups at once
+    postprocess_many(skeletons, dust_threshold=1500, tick_threshold=3000)
+
+Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
+functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
+come from one kernel call (csrc/join.hip through kimimaro_amd.points.part_gaps), the merge sequence from host C that reads only
+that table (kh_host_join_plan); they have no CPU fallback.  Written from the behaviour of the reference, including the parts that are visible in its
 results: which cycle its depth-first search reports first (skeletontricks.hpp:209-300: neighbours in the order the
 edges list them, the search starts at the first edge), float32 branch lengths accumulated outward from the smallest
 terminal node (skeletontricks.hpp:303-380), superedges fused at a branch point that drops to two edges and from then
@@ -16,10 +21,12 @@ stand-ins it needs: tests/golden/make_golden.py `post`).
 """
 from __future__ import annotations
 
+import time
 from collections import defaultdict
 
 import numpy as np
 
+from . import _abi, ops, points
 from .skeleton import Skeleton
 
 
@@ -102,6 +109,89 @@ def join_close_components(skeletons, radius=np.inf, restrict_by_radius=False):
         for j in range(1, len(parts)):
             gaps[(0, j)] = gap(tree, fused, parts[j])
     return Skeleton.simple_merge(parts).consolidate(remove_disconnected_vertices=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+def join_parts(skeletons):
+    """the parts join_close_components works on: the components of every skeleton, in order, consolidated, the empty ones dropped"""
+    if isinstance(skeletons, Skeleton):
+        skeletons = [skeletons]
+    parts = []
+    for s in skeletons:
+        parts.extend(c.consolidate(remove_disconnected_vertices=True) for c in s.components())
+    return [p for p in parts if not p.empty()]
+
+
+def join_plan(part_sizes, d2, idx, radii, radius, restrict_by_radius):
+    """kh_host_join_plan (host C, no GPU needed; include/kimi_hip.h): the edges u32 [m, 2], in the numbering of the concatenated parts,
+    that join_close_components adds to one group, from the table of nearest pairs (d2 f64 [n, n], idx u32 [n, n, 2]) of its parts."""
+    sizes = np.ascontiguousarray(part_sizes, dtype=np.uint32)
+    n = int(sizes.size)
+    d2 = np.ascontiguousarray(d2, dtype=np.float64)
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    radii = np.ascontiguousarray(radii, dtype=np.float32)
+    if d2.size != n * n or idx.size != 2 * n * n or radii.size != int(sizes.sum(dtype=np.int64)):
+        raise ValueError("join_plan: tables of %d and %d entries, %d radii for %d parts" % (d2.size, idx.size, radii.size, n))
+    edges = np.zeros((max(n - 1, 1), 2), dtype=np.uint32)
+    p = _abi.np_ptr
+    m = _abi.lib().kh_host_join_plan(n, p(sizes), p(d2), p(idx), p(radii), float(radius), int(bool(restrict_by_radius)), p(edges))
+    if m == -2:
+        raise MemoryError("kh_host_join_plan failed")
+    if m < 0:
+        raise ValueError("kh_host_join_plan: a record names a vertex outside its part")
+    return edges[:m]
+
+
+def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, timings=None):
+    """join_close_components for many groups at once: each group is a Skeleton or a sequence of them, the result per
+    group what join_close_components(group, radius, restrict_by_radius) returns -- Skeleton.simple_merge of its parts plus one edge
+    per merge, consolidated.  The nearest pairs between the parts of ALL groups come from one kernel call (a few when their tables
+    exceed 1 GiB; a single group of more than 8 192 parts is a ValueError), every group with its own radius and bound under
+    restrict_by_radius; the merge sequence of a group is decided on its table alone.  Where several tree vertices are equally near
+    the winning query vertex the smallest index is taken (cKDTree makes its own choice there).  No CPU fallback:
+    HipUnavailableError without the library or an MI355X.  timings (a dict): kernel_ms, copy_s, plan_s of the call."""
+    if radius is None:
+        radius = np.inf
+    if radius <= 0:
+        raise ValueError("radius must be greater than zero: " + str(radius))
+    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    groups = list(groups)
+    parts = [join_parts(g) for g in groups]
+    radius_of = [float(radius)] * len(groups)
+    if restrict_by_radius:
+        radius_of = [max(2 * max(float(np.max(p.radii)) for p in ps), 0) if ps else 0.0 for ps in parts]
+    todo = [g for g in range(len(groups)) if len(parts[g]) >= 2]
+    tables = points.part_gaps(eng, [[p.vertices for p in parts[g]] for g in todo],
+                              [(radius_of[g] + 0.000001) * (radius_of[g] + 0.000001) for g in todo], timings=timings)
+    out = [ps[0] if ps else Skeleton() for ps in parts]
+    t0 = time.perf_counter()
+    for g, (d2, idx) in zip(todo, tables):
+        ps = parts[g]
+        merged = Skeleton.simple_merge(ps)
+        added = join_plan([p.vertices.shape[0] for p in ps], d2, idx, merged.radii, radius_of[g], restrict_by_radius)
+        merged.edges = np.concatenate([merged.edges, added])
+        out[g] = merged.consolidate(remove_disconnected_vertices=True)
+    if timings is not None:
+        timings["plan_s"] = timings.get("plan_s", 0.0) + time.perf_counter() - t0
+    return out
+
+
+def postprocess_many(skeletons, dust_threshold=1500.0, tick_threshold=3000.0):
+    """postprocess for many skeletons: dust and loops out per skeleton on the host, the join of ALL of them in one
+    join_close_components_many(restrict_by_radius=True) call, ticks out per skeleton on the host."""
+    skeletons = list(skeletons)
+    ops.engine()                                         # raises HipUnavailableError without the library or a gfx950 device
+    cleaned = []
+    for skeleton in skeletons:
+        skel = skeleton.consolidate(remove_disconnected_vertices=True)
+        skel = remove_dust(skel, dust_threshold)
+        cleaned.append(remove_loops(skel))
+    out = []
+    for skeleton, skel in zip(skeletons, join_close_components_many(cleaned, restrict_by_radius=True)):
+        skel = remove_ticks(skel, tick_threshold)
+        skel.id = skeleton.id
+        out.append(skel.consolidate(remove_disconnected_vertices=True))
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
