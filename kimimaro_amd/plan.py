@@ -335,3 +335,52 @@ def plan_tasks(labels, params, lv, *, nlabels, order=None, rmax_t=None, max_path
     tasks["tgt_offset"] = tgt_off
     p.tgt_arr = np.asarray(tgt + [0], dtype=np.uint32)
     return p
+
+
+# -- a dataset cut into chunks ---------------------------------------------------------------------------------------------------
+class ChunkGrid(NamedTuple):
+    """What chunk_grid returns: `grid` = chunks per axis; per chunk, x fastest, int64 [n, 3]: `grid_index` (its place in the grid), the half-open
+    corners of its core (`core_lo`, `core_hi`) and of its box (`box_lo`, `box_hi`)."""
+    grid: tuple
+    grid_index: np.ndarray
+    core_lo: np.ndarray
+    core_hi: np.ndarray
+    box_lo: np.ndarray
+    box_hi: np.ndarray
+
+
+def _axis_cuts(n, c, overlap):
+    """(starts, core ends, box ends) of one axis of length n cut every c voxels"""
+    starts = np.arange(0, max(n - overlap, 1), c, dtype=np.int64)
+    core_hi = np.concatenate([starts[1:], [n]]).astype(np.int64)
+    return starts, core_hi, np.minimum(starts + c + overlap, n)
+
+
+def chunk_grid(shape, chunk_shape, overlap=1):
+    """The chunks of a dataset of `shape` voxels as a ChunkGrid.  Per axis of length n with chunk length c the starts
+    are 0, c, 2c, ... below n - overlap (0 alone when n <= overlap); the CORE of a start reaches to the next start, the last one to n:
+    the cores partition the dataset.  The BOX of a start is [start, min(start + c + overlap, n)): the core plus `overlap` voxels on the
+    high side, which are the first voxels of the next core -- both chunks see the same face there.  A trailing slab that would hold
+    nothing but the previous box's overlap never becomes a chunk (n = 97, c = 48: boxes [0, 49) and [48, 97)).  An entry of
+    chunk_shape may exceed n: one chunk, no overlap.  Two-axis shapes get a unit z axis.  ValueError: an entry that is not a
+    positive integer, a negative overlap, a shape that has not two or three axes, a chunk_shape of another length than the shape
+    (three entries are accepted for two axes)."""
+    shape, chunk_shape = tuple(shape), tuple(chunk_shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("chunk_grid: a dataset has two or three axes. Got: {}".format(shape))
+    if len(chunk_shape) != len(shape) and len(chunk_shape) != 3:
+        raise ValueError("chunk_grid: chunk_shape {} does not fit a dataset of shape {}".format(chunk_shape, shape))
+    for v in shape + chunk_shape:
+        if int(v) != v or int(v) <= 0:
+            raise ValueError("chunk_grid: extents are positive integers. Got: {} / {}".format(shape, chunk_shape))
+    if int(overlap) != overlap or int(overlap) < 0:
+        raise ValueError("chunk_grid: overlap must be a non-negative integer. Got: {}".format(overlap))
+    shape = tuple(int(v) for v in (shape + (1,))[:3])
+    chunk_shape = tuple(int(v) for v in (chunk_shape + (1,))[:3])
+    cuts = [_axis_cuts(n, c, int(overlap)) for n, c in zip(shape, chunk_shape)]
+    grid = tuple(int(c[0].size) for c in cuts)
+    kz, ky, kx = np.meshgrid(np.arange(grid[2]), np.arange(grid[1]), np.arange(grid[0]), indexing="ij")
+    index = np.stack([kx.ravel(), ky.ravel(), kz.ravel()], axis=1).astype(np.int64)          # x fastest, then y, then z
+    pick = lambda which: np.stack([cuts[ax][which][index[:, ax]] for ax in range(3)], axis=1).astype(np.int64)
+    lo = pick(0)
+    return ChunkGrid(grid, index, lo, pick(1), lo.copy(), pick(2))

@@ -6,6 +6,7 @@
 
     join_close_components_many(groups, radius=inf, restrict_by_radius)  the join of many groups at once
     postprocess_many(skeletons, dust_threshold=1500, tick_threshold=3000)
+    skeletonize_chunked(dataset, chunk_shape, ...)                      a dataset in chunks to whole skeletons
 
 Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
 functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
@@ -26,7 +27,9 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import _abi, ops, points
+from . import _abi, intake, ops, points
+from .lanes import Lanes, lanes_for
+from .plan import chunk_grid
 from .skeleton import Skeleton
 
 
@@ -192,6 +195,182 @@ def postprocess_many(skeletons, dust_threshold=1500.0, tick_threshold=3000.0):
         skel.id = skeleton.id
         out.append(skel.consolidate(remove_disconnected_vertices=True))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+def place_fragment(skeleton, box_low, anisotropy, label=None):
+    """The skeleton of one box (physical space, vertices = f32(voxel) * anisotropy) moved to where the box lies in the dataset: a new
+    Skeleton with vertices f32(voxel + box_low) * anisotropy -- the very floats a run over the whole dataset stores for those voxels, so
+    that the seam vertices of neighbouring boxes are bit-equal and consolidate() fuses them.  (Adding f32(box_low) * anisotropy to the
+    vertices instead rounds twice and misses that value for most anisotropies that are no small integers.)  The voxel of a vertex v
+    is i = rint(v / anisotropy); ValueError when f32(i) * anisotropy != v for some vertex: it does not lie on the voxel lattice.
+    Edges, radii, vertex types and transform are the skeleton's; id = `label` (default: the skeleton's), space = "physical"."""
+    an = np.asarray(anisotropy, dtype=np.float32).reshape(3)
+    low = np.asarray(box_low, dtype=np.int64).reshape(3)
+    v = np.asarray(skeleton.vertices, dtype=np.float32).reshape(-1, 3)
+    voxel = np.rint(v.astype(np.float64) / an.astype(np.float64)).astype(np.int64)
+    back = np.multiply(voxel.astype(np.float32), an, dtype=np.float32)
+    if not np.array_equal(back, v):
+        k = int(np.flatnonzero((back != v).any(axis=1))[0])
+        raise ValueError("place_fragment: vertex %d = %s is not f32(voxel) * anisotropy for anisotropy %s" % (k, v[k].tolist(), an.tolist()))
+    placed = np.multiply((voxel + low).astype(np.float32), an, dtype=np.float32)
+    return Skeleton(placed, np.array(skeleton.edges), np.array(skeleton.radii), np.array(skeleton.vertex_types),
+                    segid=skeleton.id if label is None else label, transform=np.array(skeleton.transform), space="physical")
+
+
+def route_targets(targets, grid, shape):
+    """Extra targets given as voxels of the dataset -> per chunk of `grid` the list of those its box contains, as (x, y, z) tuples
+    relative to the box's low corner.  A point on an overlap plane goes to both boxes.  Two coordinates get z = 0.  IndexError, naming
+    the point, for one outside a dataset of `shape`."""
+    shape = (tuple(int(v) for v in shape) + (1,))[:3]
+    out = [[] for _ in range(grid.box_lo.shape[0])]
+    for target in targets:
+        pt = tuple(int(v) for v in target)
+        if len(pt) == 2:
+            pt += (0,)
+        if len(pt) != 3 or any(not 0 <= v < s for v, s in zip(pt, shape)):
+            raise IndexError("point {} is outside a dataset of shape {}".format(tuple(target), shape))
+        p = np.asarray(pt, dtype=np.int64)
+        for k in np.flatnonzero(((grid.box_lo <= p) & (p < grid.box_hi)).all(axis=1)).tolist():
+            out[k].append(tuple(int(v) for v in p - grid.box_lo[k]))
+    return out
+
+
+def _load_box(dataset, lo, hi):
+    """dataset[lo:hi] as a host array with three axes: numpy arrays of any order and memmaps, a tensor (copied from where it lives),
+    anything that takes a tuple of slices (the h5py / zarr form)"""
+    cut = dataset[tuple(slice(int(a), int(b)) for a, b in zip(lo, hi))[:len(dataset.shape)]]
+    if hasattr(cut, "cpu") and hasattr(cut, "numpy"):
+        cut = cut.cpu().numpy()
+    cut = np.asarray(cut)
+    return cut.reshape(cut.shape + (1,) * (3 - cut.ndim))
+
+
+def count_labels(dataset, grid):
+    """{label: voxels in the whole dataset}, zero included, from one pass over the cores of `grid` (they partition the dataset)"""
+    total = defaultdict(int)
+    for lo, hi in zip(grid.core_lo, grid.core_hi):
+        values, counts = np.unique(_load_box(dataset, lo, hi), return_counts=True)
+        for value, count in zip(values.tolist(), counts.tolist()):
+            total[value] += count
+    return dict(total)
+
+
+def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None, anisotropy=(1, 1, 1), object_ids=None,
+                        dust_threshold=1000, dust_global=False, post_dust_threshold=1500.0, tick_threshold=3000.0, merge=True,
+                        fix_branching=True, fix_borders=True, fill_holes=False, fix_avocados=False, extra_targets_before=[],
+                        extra_targets_after=[], progress=False, lanes=None, width=None, timings=None, _skeletonize=None,
+                        _postprocess=None):
+    """A dataset in chunks to whole skeletons, {label: Skeleton} in ascending label order: what igneous does around
+    kimimaro.skeletonize and kimimaro.postprocess, in one call.
+
+    The dataset is cut by plan.chunk_grid(dataset.shape, chunk_shape): every box shares its last plane with the next core, so with
+    fix_borders a label that crosses a cut gets the same path end in both boxes.  Every box goes through skeletonize with several
+    in flight (kimimaro_amd.lanes; a box is loaded by the lane that takes it, so loading overlaps tracing); the fragments are
+    moved into dataset coordinates (place_fragment) and, per label, fused: Skeleton.simple_merge(fragments).consolidate().  ONE
+    postprocess_many(fused skeletons, post_dust_threshold, tick_threshold) follows; a label whose result is empty is dropped.  The
+    result is DEFINED as this composition; it is not skeletonize() of the whole volume.
+
+    dataset: a numpy array of any memory order, an np.memmap, a tensor on the GPU, or any object with .shape and __getitem__ over a
+      tuple of slices; two or three axes.  It may hold 2^32 voxels or more: only a box has to stay below that.
+    teasar_params, anisotropy, object_ids, fix_branching, fix_borders, fill_holes, fix_avocados: handed to skeletonize per box.
+    dust_threshold: skeletonize's, per box and component (the reference's meaning) -- unless
+    dust_global: a label is kept when it has more than dust_threshold voxels in the WHOLE dataset (counted in a first pass over the
+      cores); every box is traced with dust_threshold=0 and object_ids = the kept labels present in it (intersected with a given
+      object_ids), a box without one is skipped.  A label cut into pieces that are each below the threshold survives only this way.
+    extra_targets_before / _after: voxels of the dataset; each goes to every box that contains it.  IndexError for one outside.
+    merge=False: {label: [placed fragments in chunk order]}, nothing further is run.
+    lanes, width: as in skeletonize_many -- a Lanes object to reuse, else `width` lanes are made (default: lanes_for() on the
+      largest box), never more than there are chunks.
+    progress: accepted, no effect.
+    timings (a dict) receives count_s, chunks_s, place_s, fuse_s, post_s (seconds), chunks (boxes traced), fragments and vertices
+      (of the placed fragments).
+    _skeletonize(labels, **kwargs) -> {label: Skeleton} runs the boxes one after the other in place of the lanes,
+    _postprocess(skeletons, dust_threshold, tick_threshold) -> list replaces postprocess_many: with both, nothing here touches the GPU
+      (the host-logic tests run the whole driver on the CPU oracle).  Without them there is no CPU fallback."""
+    params = intake.DEFAULT_TEASAR_PARAMS if teasar_params is None else teasar_params
+    if _skeletonize is None or (merge and _postprocess is None):
+        ops.engine()                                     # raises HipUnavailableError without the library or a gfx950 device
+    shape = tuple(int(v) for v in dataset.shape)
+    if len(shape) not in (2, 3):
+        raise intake.DimensionError("skeletonize_chunked needs a dataset of two or three axes. Got: {}".format(shape))
+    grid = chunk_grid(shape, chunk_shape)
+    n = int(grid.box_lo.shape[0])
+    extents = grid.box_hi - grid.box_lo
+    largest = tuple(int(v) for v in extents[int(np.argmax(np.prod(extents, axis=1)))])
+    if largest[0] * largest[1] * largest[2] >= 2 ** 32:
+        raise ValueError("skeletonize_chunked: a box of {} voxels does not fit the 32-bit indices of a volume".format(largest))
+    before = route_targets(extra_targets_before, grid, shape)
+    after = route_targets(extra_targets_after, grid, shape)
+    wanted = None if object_ids is None else set(int(v) for v in object_ids)
+
+    t0 = time.perf_counter()
+    kept = None
+    if dust_global:
+        kept = {label for label, count in count_labels(dataset, grid).items() if label != 0 and count > dust_threshold}
+        if wanted is not None:
+            kept &= wanted
+    count_s = time.perf_counter() - t0
+
+    def one(k, run):
+        labels = _load_box(dataset, grid.box_lo[k], grid.box_hi[k])
+        ids, dust = object_ids, dust_threshold
+        if kept is not None:
+            ids = sorted(kept.intersection(np.unique(labels).tolist()))
+            dust = 0
+            if not ids:
+                return None
+        return run(labels, teasar_params=params, anisotropy=anisotropy, object_ids=ids, dust_threshold=dust, progress=False,
+                   fix_branching=fix_branching, fix_borders=fix_borders, fill_holes=fill_holes, fix_avocados=fix_avocados,
+                   extra_targets_before=before[k], extra_targets_after=after[k])
+
+    t0 = time.perf_counter()
+    if _skeletonize is not None:
+        results = [one(k, _skeletonize) for k in range(n)]
+    else:
+        own = lanes is None
+        if own:
+            if width is None:
+                import torch
+                width = lanes_for(largest, torch.cuda.mem_get_info()[0])
+            lanes = Lanes(max(1, min(n, int(width))))
+
+        def job(eng, k):
+            return one(k, lambda labels, **kw: intake.skeletonize(labels, _engine=eng, **kw))
+
+        try:
+            results = [res for _, res in lanes.run(job, n)]
+        finally:
+            if own:
+                lanes.close()
+    chunks_s = time.perf_counter() - t0
+
+    t0 = time.perf_counter()
+    fragments = defaultdict(list)
+    for k, res in enumerate(results):
+        for label, skel in (res or {}).items():
+            if not skel.empty():
+                fragments[label].append(place_fragment(skel, grid.box_lo[k], anisotropy, label=label))
+    fragments = {label: fragments[label] for label in sorted(fragments)}
+    place_s = time.perf_counter() - t0
+    if timings is not None:
+        timings.update(count_s=count_s, chunks_s=chunks_s, place_s=place_s, fuse_s=0.0, post_s=0.0,
+                       chunks=sum(res is not None for res in results), fragments=sum(len(f) for f in fragments.values()),
+                       vertices=sum(s.vertices.shape[0] for f in fragments.values() for s in f))
+    if not merge:
+        return fragments
+
+    t0 = time.perf_counter()
+    fused = [Skeleton.simple_merge(f).consolidate() for f in fragments.values()]
+    fuse_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    done = []
+    if fused:
+        done = (postprocess_many if _postprocess is None else _postprocess)(fused, post_dust_threshold, tick_threshold)
+    post_s = time.perf_counter() - t0
+    if timings is not None:
+        timings.update(fuse_s=fuse_s, post_s=post_s)
+    return {label: skel for label, skel in zip(fragments, done) if not skel.empty()}
 
 
 # ---------------------------------------------------------------------------------------------------------------
