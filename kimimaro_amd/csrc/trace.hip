@@ -1111,7 +1111,7 @@ __device__ __forceinline__ void sweep_setup(Sweep& sw, SweepShared* swsh, Ctl* c
   if (!windowed && nlev > sg.lds_levels) nlev = 0u;
   sw.nslots = windowed ? win : nlev;
   sw.wmask = windowed ? win - 1u : 0xFFFFFFFFu;
-  // arena: [spill table: ev_spill keys (u32) + ev_spill candidate words (u64)][(free stack of rounds 4-5: unused)][chunks]
+  // arena: [spill table: ev_spill candidate words (u64) + ev_spill keys (u32)][(free stack of rounds 4-5: unused)][chunks]
   gbyte_t* fsp = (gbyte_t*)(sg.arena + (size_t)task->ev_offset * 256u);
   const uint32_t spcap = task->ev_spill;          // 0 or a power of two
   sw.spcap = (spcap & (spcap - 1u)) == 0u ? spcap : 0u;

@@ -473,10 +473,13 @@ class Engine:
         return hit[0], hit[1], hit[2], covered
 
     # -- one binary object on its own (the function-level mirrors of ops.py) ---------------
-    def single_object(self, mask, anisotropy, rmax=0.0, dbf=None, voxel_graph=None):
+    def single_object(self, mask, anisotropy, rmax=0.0, dbf=None, voxel_graph=None, window_cap=0, window_cap_always=False,
+                      arena_divisor=1):
         """Device context of ONE binary object given as a host mask (x, y, z; Fortran order): component volume (0 / 1),
         voxel list, neighbour masks, per-label scratch and -- for ball radii up to `rmax` -- the level table and the
-        event arena of the invalidation sweep.  Returns a dict of device tensors + the kh_label_t record."""
+        event arena of the invalidation sweep.  Returns a dict of device tensors + the kh_label_t record.
+        window_cap, window_cap_always, arena_divisor: the planner's knobs (plan.plan_sweep) for a smaller level window or event
+        arena than the object is entitled to; a call that runs out of either is redone by the heap emulation (tests)."""
         t = self.torch
         lib = self.lib
         P = self.ptr
@@ -522,8 +525,9 @@ class Engine:
                    d_heap=self.empty(2 * hcap, t.int64), d_qstate=t.zeros(nvox + 4, dtype=t.uint8, device=self.device))
         rmax = float(np.float32(rmax))
         lv = self.sweep_levels(shape, anisotropy, [rmax], [cnt]) if self.sweep and cnt > 0 and np.isfinite(rmax) and rmax > 0 else None
-        # (no window cap, no arena divisor; keep_unfit: this record books arena and spill table whatever the levels fit)
-        sw = plan_sweep([cnt], np.array([rmax], dtype=np.float32), lv, lds_levels=self.sweep_lds_levels, keep_unfit=True)
+        # (by default no window cap and no arena divisor; keep_unfit: this record books arena and spill table whatever the levels fit)
+        sw = plan_sweep([cnt], np.array([rmax], dtype=np.float32), lv, window_cap=window_cap, window_cap_always=window_cap_always,
+                        arena_divisor=arena_divisor, lds_levels=self.sweep_lds_levels, keep_unfit=True)
         for key in SWEEP_FIELDS:
             task[key] = getattr(sw, key)
         sweep_on, max_nlev, ev_units = sw.sweep_on, sw.max_nlev, sw.ev_total
