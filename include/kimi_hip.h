@@ -542,6 +542,27 @@ int kh_cross_sections_filled(const void* labels, int label_bytes, int64_t sx, in
                              const uint32_t* region, const uint32_t* hole_begin, const uint32_t* hole_count,
                              const uint32_t* hole_regions, float* area, uint8_t* contact, uint32_t* voxels, void* scratch,
                              int64_t scratch_bytes, void* stream);
+/* kimimaro_amd.cross_sectional_area_chunked: kh_cross_sections for a label array that is the box [o, o + b) of a
+ * dataset of extents d, b = (sx, sy, sz); o and d are 64-bit and the dataset may hold 2^32 voxels or more, only the box obeys the
+ * limits of kh_cross_sections.  seed_lin are linear indices IN THE BOX.  The box must lie inside the dataset.
+ * contact[i] refers to the DATASET: bit 0 some section voxel has dataset coordinate x + ox == 0, bit 1 x + ox == dx-1, and so on.
+ * clip[i]    the same bit layout for the faces of the BOX that are no faces of the dataset: bit 0 x == 0 && ox > 0, bit 1
+ *            x == sx-1 && ox + sx < dx, ...  clip == 0: every neighbour of every section voxel lay inside the box, the section is the
+ *            voxel set a launch on the whole dataset finds.  Otherwise it is a subset of that and area / voxels are lower bounds.
+ * The fixed point of the sum is 2^(62 - fixed_exponent), the caller's: kh_cross_sections_fixed_exponent of the DATASET makes the
+ * integer sum of a section with clip == 0 the one kh_cross_sections computes on the whole dataset, and area bit-equal.  It must not
+ * be smaller than the box's own exponent (bad argument), which keeps every sum below 2^62.
+ * scratch: kh_cross_sections_scratch_bytes of the BOX's extents.  Everything else as kh_cross_sections; clip is 0 for an empty
+ * section.  There is no filled variant.
+ * kh_cross_sections_fixed_exponent (host, no device needed): the e kh_cross_sections uses for a volume of extents (dx, dy, dz), each
+ * below 2^31, with the anisotropy (ax, ay, az): the binary exponent of ((ax*ay + ay*az) + ax*az) * min(4 * largest face, dx*dy*dz),
+ * the face exact in 64 bits, the other products float64.  INT32_MIN for extents or an anisotropy the launches refuse, or a
+ * bound that is not a positive finite float64.                                                                                   */
+int kh_cross_sections_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay, double az,
+                          int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals, int64_t ox,
+                          int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz, int fixed_exponent, float* area,
+                          uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch, int64_t scratch_bytes, void* stream);
+int kh_cross_sections_fixed_exponent(int64_t dx, int64_t dy, int64_t dz, double ax, double ay, double az);
 /* host: the membership test and the area of ONE voxel at offset (dx, dy, dz) from the seed, by the functions the kernel runs
  * (normal, anisotropy: f64 [3]).  Returns 1 if the voxel is cut; *offset = d, *half_width = h, *area = area(plane /\ box).      */
 int kh_host_section_voxel(const double* normal, const double* anisotropy, int64_t dx, int64_t dy, int64_t dz, double* offset,

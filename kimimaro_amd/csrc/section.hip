@@ -21,6 +21,13 @@
 // The FILLED instantiation (kh_cross_sections_filled) cuts filled(L) = L u hole(L) instead of L: "carries the item's label" becomes
 // "carries it, or lies in one of the regions (kh_regions6) that the item's sorted list names".  Only that test differs; an item
 // with an empty list reads no region at all.
+//
+// The BOX instantiation (kh_cross_sections_box) is handed the box [o, o + b) of a dataset of extents d instead of a whole volume.
+// The flood and the hot loop are the same statements: `touch` collects the faces of the ARRAY the flood reaches, as ever.  A face of
+// the box either is a face of the dataset (o == 0, o + b == d) or a cut through it, a property of the launch and not of the voxel, so
+// the epilogue splits the one accumulator by a mask: contact = touch & dataset_faces, clip = touch & ~dataset_faces.  The fixed
+// point's quantum comes from the caller (the dataset's, kh_cross_sections_fixed_exponent), so that a section no cut clips sums to
+// the same integer in every box and in the whole dataset.
 #include <math.h>
 
 #include "common.h"
@@ -122,8 +129,15 @@ __device__ inline bool xs_listed(const uint32_t* __restrict__ list, uint32_t n, 
   return lo < n && list[lo] == r;
 }
 
-template <typename LT, bool FILLED>
-__global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel(const LT* __restrict__ lab, XsArgs p, XsHoles hs) {
+// the box of a dataset (BOX): which faces of the label array are faces of the dataset (the bits of `contact`), and where the others go
+struct XsBox {
+  uint32_t dataset_faces;
+  uint8_t* clip;
+};
+
+template <typename LT, bool FILLED, bool BOX>
+__global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel(const LT* __restrict__ lab, XsArgs p, XsHoles hs,
+                                                                                 XsBox bx) {
   __shared__ uint32_t lds_queue[XS_WAVES_PER_BLOCK][XS_LDS_QUEUE];
   const int lane = (int)(threadIdx.x & 63);
   const int wave_in_block = (int)(threadIdx.x >> 6);
@@ -167,6 +181,7 @@ __global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel
         p.area[item] = 0.0f;
         p.contact[item] = 0;
         p.voxels[item] = 0;
+        if (BOX) bx.clip[item] = 0;
       }
       continue;
     }
@@ -292,7 +307,8 @@ __global__ __launch_bounds__(64 * XS_WAVES_PER_BLOCK) void cross_sections_kernel
     }
     if (lane == 0) {
       p.area[item] = (float)((double)fixed * p.fixed_inverse);
-      p.contact[item] = (uint8_t)touch;
+      p.contact[item] = (uint8_t)(BOX ? touch & bx.dataset_faces : touch);
+      if (BOX) bx.clip[item] = (uint8_t)(touch & ~bx.dataset_faces);
       p.voxels[item] = count;
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
@@ -319,9 +335,31 @@ static bool xs_layout(int64_t sx, int64_t sy, int64_t sz, XsLayout& L) {
   return true;
 }
 
+// e with (the largest possible sum of a section of a volume of these extents) < 2^e: a voxel's polygon is no larger than the three
+// faces of its box together, a section has at most min(4 x the largest face, the volume) voxels.  Extents up to 2^31 each: the face
+// is exact in 64 bits, the products beyond that are float64.  False for extents or an anisotropy the launches refuse, and for a
+// bound that float64 does not hold (e is frexp's then, as it always was).
+static bool xs_fixed_exponent(int64_t sx, int64_t sy, int64_t sz, double ax, double ay, double az, int& e) {
+  if (sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) || sy >= (1ll << 31) || sz >= (1ll << 31)) return false;
+  if (!(ax > 0 && ay > 0 && az > 0) || !isfinite(ax) || !isfinite(ay) || !isfinite(az)) return false;
+  int64_t face = sx * sy;
+  if (sx * sz > face) face = sx * sz;
+  if (sy * sz > face) face = sy * sz;
+  const double most = 4.0 * (double)face, nv = ((double)sx * (double)sy) * (double)sz;
+  const double sum = ((ax * ay + ay * az) + ax * az) * (most < nv ? most : nv);
+  e = 0;
+  frexp(sum, &e);       // sum < 2^e
+  return isfinite(sum) && sum > 0.0;
+}
+
 }  // namespace kh
 
 using namespace kh;
+
+extern "C" int kh_cross_sections_fixed_exponent(int64_t dx, int64_t dy, int64_t dz, double ax, double ay, double az) {
+  int e = 0;
+  return xs_fixed_exponent(dx, dy, dz, ax, ay, az, e) ? e : INT32_MIN;
+}
 
 extern "C" int64_t kh_cross_sections_scratch_bytes(int64_t sx, int64_t sy, int64_t sz, int64_t n_waves) {
   XsLayout L;
@@ -329,11 +367,12 @@ extern "C" int64_t kh_cross_sections_scratch_bytes(int64_t sx, int64_t sy, int64
   return XS_HEADER_BYTES + n_waves * L.wave_bytes;
 }
 
-// both entry points: hs == nullptr launches the plain instantiation, `name` heads the error messages
+// all entry points: hs == nullptr && bx == nullptr launches the plain instantiation, `name` heads the error messages;
+// fixed_exponent is read with bx alone
 static int xs_launch(const char* name, const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
                      double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals,
-                     const XsHoles* hs, float* area, uint8_t* contact, uint32_t* voxels, void* scratch, int64_t scratch_bytes,
-                     void* stream) {
+                     const XsHoles* hs, const XsBox* bx, int fixed_exponent, float* area, uint8_t* contact, uint32_t* voxels,
+                     void* scratch, int64_t scratch_bytes, void* stream) {
   if (int rc = require_device()) return rc;
   XsLayout L;
   if (!xs_layout(sx, sy, sz, L)) {
@@ -377,17 +416,29 @@ static int xs_launch(const char* name, const void* labels, int label_bytes, int6
   // stays below 2^62 quanta.  The quantum is then below 2^-30 of one voxel's area even for 2^32 voxels -- far below half a
   // float32 ulp of any sum.
   int e = 0;
-  frexp(((ax * ay + ay * az) + ax * az) * (double)L.queue_cap, &e);       // value < 2^e
+  xs_fixed_exponent(sx, sy, sz, ax, ay, az, e);
+  if (bx) {
+    // the caller's quantum: never finer than this array's own (the sums stay below 2^62), and 2^(62 - e) stays a normal double
+    if (fixed_exponent < e || fixed_exponent > 1023) {
+      set_error("%s: fixed_exponent %d, at least this box's own (%d: kh_cross_sections_fixed_exponent of the dataset)", name,
+                fixed_exponent, e);
+      return KH_EINVAL;
+    }
+    e = fixed_exponent;
+  }
   p.fixed_scale = ldexp(1.0, 62 - e);
   p.fixed_inverse = ldexp(1.0, e - 62);
   KH_HIP_CHECK(hipMemsetAsync(scratch, 0, (size_t)(XS_HEADER_BYTES + waves * L.bitmap_words * 4), st));
   const unsigned grid = (unsigned)((waves + XS_WAVES_PER_BLOCK - 1) / XS_WAVES_PER_BLOCK);
   const dim3 block(64 * XS_WAVES_PER_BLOCK);
   const XsHoles none = {nullptr, nullptr, nullptr, nullptr};
-#define KH_XS_LAUNCH(LT)                                                                                                  \
-  do {                                                                                                                    \
-    if (hs) hipLaunchKernelGGL((cross_sections_kernel<LT, true>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs);    \
-    else hipLaunchKernelGGL((cross_sections_kernel<LT, false>), dim3(grid), block, 0, st, (const LT*)labels, p, none);     \
+  const XsBox whole = {63u, nullptr};
+#define KH_XS_LAUNCH(LT)                                                                                                              \
+  do {                                                                                                                                \
+    if (hs) hipLaunchKernelGGL((cross_sections_kernel<LT, true, false>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs, whole);  \
+    else if (bx) hipLaunchKernelGGL((cross_sections_kernel<LT, false, true>), dim3(grid), block, 0, st, (const LT*)labels, p, none,    \
+                                    *bx);                                                                                             \
+    else hipLaunchKernelGGL((cross_sections_kernel<LT, false, false>), dim3(grid), block, 0, st, (const LT*)labels, p, none, whole);   \
   } while (0)
   switch (label_bytes) {
     case 1: KH_XS_LAUNCH(uint8_t); break;
@@ -405,7 +456,7 @@ extern "C" int kh_cross_sections(const void* labels, int label_bytes, int64_t sx
                                  const double* normals, float* area, uint8_t* contact, uint32_t* voxels, void* scratch,
                                  int64_t scratch_bytes, void* stream) {
   return xs_launch("kh_cross_sections", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, nullptr,
-                   area, contact, voxels, scratch, scratch_bytes, stream);
+                   nullptr, 0, area, contact, voxels, scratch, scratch_bytes, stream);
 }
 
 extern "C" int kh_cross_sections_filled(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
@@ -415,7 +466,30 @@ extern "C" int kh_cross_sections_filled(const void* labels, int label_bytes, int
                                         uint32_t* voxels, void* scratch, int64_t scratch_bytes, void* stream) {
   const XsHoles hs = {region, hole_begin, hole_count, hole_regions};
   return xs_launch("kh_cross_sections_filled", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, &hs,
-                   area, contact, voxels, scratch, scratch_bytes, stream);
+                   nullptr, 0, area, contact, voxels, scratch, scratch_bytes, stream);
+}
+
+extern "C" int kh_cross_sections_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                                     double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                     const double* normals, int64_t ox, int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz,
+                                     int fixed_exponent, float* area, uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch,
+                                     int64_t scratch_bytes, void* stream) {
+  const char* name = "kh_cross_sections_box";
+  if (ox < 0 || oy < 0 || oz < 0 || sx <= 0 || sy <= 0 || sz <= 0 || dx <= 0 || dy <= 0 || dz <= 0 || ox > dx - sx || oy > dy - sy ||
+      oz > dz - sz) {
+    set_error("%s: the box [o, o + b) must lie inside the dataset [0, d)", name);
+    return KH_EINVAL;
+  }
+  if (!clip && n_items > 0) {
+    set_error("%s: clip must not be null", name);
+    return KH_EINVAL;
+  }
+  XsBox bx;
+  bx.dataset_faces = (ox == 0 ? 1u : 0u) | (ox + sx == dx ? 2u : 0u) | (oy == 0 ? 4u : 0u) | (oy + sy == dy ? 8u : 0u) |
+                     (oz == 0 ? 16u : 0u) | (oz + sz == dz ? 32u : 0u);
+  bx.clip = clip;
+  return xs_launch(name, labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, nullptr, &bx,
+                   fixed_exponent, area, contact, voxels, scratch, scratch_bytes, stream);
 }
 
 // host: the membership test and the per-voxel area of one voxel at offset (dx, dy, dz) from the seed -- the same inline functions

@@ -384,3 +384,26 @@ def chunk_grid(shape, chunk_shape, overlap=1):
     pick = lambda which: np.stack([cuts[ax][which][index[:, ax]] for ax in range(3)], axis=1).astype(np.int64)
     lo = pick(0)
     return ChunkGrid(grid, index, lo, pick(1), lo.copy(), pick(2))
+
+
+def halo_boxes(shape, chunk_shape, halo):
+    """The cores and boxes of cross_sectional_area_chunked -> (core_lo, core_hi, box_lo, box_hi), int64 [n, 3], half
+    open, x fastest: the cores of chunk_grid(shape, chunk_shape, overlap=0), which partition the dataset, and per core its box: the
+    core widened by `halo` voxels on all six sides, clamped to the dataset.  ValueError as chunk_grid, and for a negative halo."""
+    if int(halo) != halo or int(halo) < 0:
+        raise ValueError("halo_boxes: halo must be a non-negative integer. Got: {}".format(halo))
+    grid = chunk_grid(shape, chunk_shape, overlap=0)
+    extent = np.array((tuple(int(v) for v in shape) + (1,))[:3], dtype=np.int64)
+    return grid.core_lo, grid.core_hi, np.maximum(grid.core_lo - int(halo), 0), np.minimum(grid.core_hi + int(halo), extent)
+
+
+def core_of(vox, shape, chunk_shape):
+    """vox (n, 3) integer voxels of a dataset of `shape` -> int64 [n]: the row of halo_boxes / chunk_grid(overlap=0) whose core holds
+    each voxel, -1 for a voxel outside the dataset.  Two-axis shapes get a unit z axis."""
+    vox = np.asarray(vox, dtype=np.int64).reshape(-1, 3)
+    extent = np.array((tuple(int(v) for v in shape) + (1,))[:3], dtype=np.int64)
+    chunk = np.array((tuple(int(v) for v in chunk_shape) + (1,))[:3], dtype=np.int64)
+    grid = (extent + chunk - 1) // chunk
+    k = vox // chunk
+    inside = np.all((vox >= 0) & (vox < extent), axis=1)
+    return np.where(inside, k[:, 0] + grid[0] * (k[:, 1] + grid[1] * k[:, 2]), -1)

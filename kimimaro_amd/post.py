@@ -7,6 +7,7 @@
     join_close_components_many(groups, radius=inf, restrict_by_radius)  the join of many groups at once
     postprocess_many(skeletons, dust_threshold=1500, tick_threshold=3000)
     skeletonize_chunked(dataset, chunk_shape, ...)                      a dataset in chunks to whole skeletons
+    cross_sectional_area_chunked(dataset, skeletons, chunk_shape, halo) their sections, the dataset in boxes
 
 Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
 functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
@@ -27,10 +28,11 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import _abi, intake, ops, points
+from . import _abi, intake, ops, points, section, utility
 from .lanes import Lanes, lanes_for
-from .plan import chunk_grid
+from .plan import chunk_grid, core_of, halo_boxes
 from .skeleton import Skeleton
+from .volume import _device_labels
 
 
 def postprocess(skeleton, dust_threshold=1500.0, tick_threshold=3000.0):
@@ -260,7 +262,7 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
                         dust_threshold=1000, dust_global=False, post_dust_threshold=1500.0, tick_threshold=3000.0, merge=True,
                         fix_branching=True, fix_borders=True, fill_holes=False, fix_avocados=False, extra_targets_before=[],
                         extra_targets_after=[], progress=False, lanes=None, width=None, timings=None, _skeletonize=None,
-                        _postprocess=None):
+                        _postprocess=None, cross_sectional_area=None):
     """A dataset in chunks to whole skeletons, {label: Skeleton} in ascending label order: what igneous does around
     kimimaro.skeletonize and kimimaro.postprocess, in one call.
 
@@ -280,6 +282,8 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
       object_ids), a box without one is skipped.  A label cut into pieces that are each below the threshold survives only this way.
     extra_targets_before / _after: voxels of the dataset; each goes to every box that contains it.  IndexError for one outside.
     merge=False: {label: [placed fragments in chunk order]}, nothing further is run.
+    cross_sectional_area: None, or a dict of keyword arguments for cross_sectional_area_chunked(dataset, result, ...), which then gives
+      every returned skeleton its sections (`anisotropy` defaults to this call's); ignored with merge=False.
     lanes, width: as in skeletonize_many -- a Lanes object to reuse, else `width` lanes are made (default: lanes_for() on the
       largest box), never more than there are chunks.
     progress: accepted, no effect.
@@ -370,7 +374,198 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
     post_s = time.perf_counter() - t0
     if timings is not None:
         timings.update(fuse_s=fuse_s, post_s=post_s)
-    return {label: skel for label, skel in zip(fragments, done) if not skel.empty()}
+    out = {label: skel for label, skel in zip(fragments, done) if not skel.empty()}
+    if cross_sectional_area is not None:
+        cross_sectional_area_chunked(dataset, out, **dict({"anisotropy": anisotropy}, **cross_sectional_area))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+XS_CLIPPED = 64          # cross_sectional_area_contacts: the section was still clipped by the largest box that could be loaded
+
+
+def _xs_box_budget(eng, itemsize):
+    """The default max_box_voxels: what the free HBM pays for.  While a box is resident a voxel costs the label itself and, in round
+    0, the copy of the core that is counted (2 x itemsize); labels of eight bytes are renumbered per box (utility._narrow_labels:
+    torch.unique with its inverse -- the sorted copy, the permutation, the inverse and the shifted ids at 8 bytes each, the u32 ids,
+    a mask: 56 bytes with the volume).  Kept back: the kernel's scratch (section.SCRATCH_BUDGET) and 1 GiB for the 2^24-voxel pieces
+    of the count."""
+    free = int(eng.torch.cuda.mem_get_info(eng.device)[0])
+    return max(0, (free - section.SCRATCH_BUDGET - (1 << 30)) // (2 * itemsize if itemsize < 8 else 56))
+
+
+def cross_sectional_area_chunked(dataset, skeletons, chunk_shape=(512, 512, 512), halo=64, anisotropy=(1, 1, 1), smoothing_window=1,
+                                 step=1, multipass=False, repair_contacts=False, max_box_voxels=None, progress=False, timings=None,
+                                 fill_holes=False, visualize_section_planes=False, _sections=None):
+    """kimimaro_amd.cross_sectional_area for a dataset that is never resident as a whole: the other half of what
+    igneous does around kimimaro.  The result is DEFINED as what cross_sectional_area(whole dataset, skeletons, ...) returns, bit for
+    bit in cross_sectional_area and equal in cross_sectional_area_contacts (whose bits name the faces of the DATASET), wherever a
+    box large enough could be loaded; the dataset may hold 2^32 voxels or more, which cross_sectional_area refuses.
+
+    dataset: what skeletonize_chunked takes.  skeletons: a dict, a list or one Skeleton, vertices in DATASET coordinates (what
+    skeletonize_chunked returns); changed in place and returned.  anisotropy, smoothing_window, step, multipass, repair_contacts,
+    the attributes, the extra_attributes entries and the skip rules: cross_sectional_area's.
+
+    The (vertex, normal) pairs are made once from the whole skeletons, so a path that crosses a cut has the normals of an unchunked
+    run.  The cores of plan.halo_boxes(dataset.shape, chunk_shape, halo) partition the dataset.  Round 0 visits every core once,
+    loads its box (the core widened by `halo` voxels, clamped), counts the skeletons' labels in the core and runs the sections whose
+    vertex lies in the core in one launch (kh_cross_sections_box).  A section that reached a face of its box that is a cut through
+    the dataset (clip != 0) is run again in round r = 1, 2, ... in the box of its core at halo * 2^r, those sections alone, until
+    none is clipped: a box equal to the dataset clips nothing.  Boxes run one after the other on one engine.
+
+    max_box_voxels: the largest box that is loaded (default: sized from the free HBM, _xs_box_budget); never 2^32 - 1 voxels or more.
+    A section whose next box would exceed it keeps its last values and gets bit 64 in cross_sectional_area_contacts: "clipped by
+    the largest box tried, the area may be an underestimate" (bits 1..32 keep cross_sectional_area's meaning).  ValueError when
+    a box of round 0 does not fit already, and for halo < 1.
+    Where cross_sectional_area launches again (a vertex whose area came back 0 and that occurs again on another path), the boxes
+    start again at `halo`.  fill_holes=True and visualize_section_planes=True raise NotImplementedError; progress: no effect.
+    timings (a dict) receives calls (per launch of the driver loop a dict of `boxes` loaded and `items` run, one entry per growth
+    round), cores, boxes_loaded, voxels_loaded, items (round 0), items_rerun (growth rounds), capped_items, kernel_ms (HIP events),
+    load_s (host: loading, upload, counting), and rounds, vertices, occurrences of the driver loop.
+    _sections: a function with the signature of section.cross_sections_box that runs the boxes instead; it is handed the box as the
+    host array and the labels themselves as words, and nothing here touches the GPU (the host-logic tests).  Without it there is no
+    CPU fallback: HipUnavailableError without the library or an MI355X."""
+    utility._xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    if fill_holes:
+        raise NotImplementedError("cross_sectional_area_chunked(fill_holes=True): the holes of a label are a property of the whole "
+                                  "dataset, not of a box (DESIGN.md 3.16)")
+    if int(halo) != halo or int(halo) < 1:
+        raise ValueError("cross_sectional_area_chunked: halo must be a positive integer. Got: {}".format(halo))
+    eng = ops.engine() if _sections is None else None    # raises HipUnavailableError without the library or a gfx950 device
+    run_sections = section.cross_sections_box if _sections is None else _sections
+    an = utility._xs_anisotropy(anisotropy)
+    an64 = an.astype(np.float64)
+    shape = tuple(int(v) for v in dataset.shape)
+    if len(shape) not in (2, 3):
+        raise intake.DimensionError("cross_sectional_area_chunked needs a dataset of two or three axes. Got: {}".format(shape))
+    core_lo, core_hi, _, _ = halo_boxes(shape, chunk_shape, 0)
+    shape = (shape + (1,))[:3]
+    extent = np.array(shape, dtype=np.int64)
+    n_cores = int(core_lo.shape[0])
+    dtype = _load_box(dataset, (0, 0, 0), (1, 1, 1)).dtype
+    if dtype != np.bool_ and dtype.kind not in "ui":
+        raise TypeError("labels must be integers or bool")
+    is_bool = dtype == np.bool_
+    span = (0, 1) if is_bool else (int(np.iinfo(dtype).min), int(np.iinfo(dtype).max))
+    limit = 2 ** 32 - 2
+    if max_box_voxels is None and eng is not None:
+        max_box_voxels = _xs_box_budget(eng, dtype.itemsize)
+    if max_box_voxels is not None:
+        limit = min(limit, int(max_box_voxels))
+
+    skels = utility._skeleton_list(skeletons)
+    labels_of = [utility._label_of(s, is_bool) for s in skels]
+    table = sorted({L for L in labels_of if L is not None})              # a job's word: the place of its label here
+    place = {L: k for k, L in enumerate(table)}
+    jobs = [(s, place[L], (0, 0, 0)) for s, L in zip(skels, labels_of) if L is not None]
+    kept = [(getattr(s, "cross_sectional_area", None), getattr(s, "cross_sectional_area_contacts", None)) for s, _, _ in jobs]
+    counts = np.zeros(len(table), dtype=np.int64)                        # voxels per label, from the cores of the first sweep
+    total = dict(calls=[], cores=n_cores, boxes_loaded=0, voxels_loaded=0, items=0, items_rerun=0, capped_items=0, load_s=0.0)
+    stats, state = {}, {"counted": False}
+    none = np.zeros(0, dtype=np.int64)
+
+    def box_labels(host, lo, k, count):
+        """-> (the box for run_sections, bytes per label, per entry of `table` the word it has in this box or -1)"""
+        words = np.full(len(table), -1, dtype=np.int64)
+        inner = tuple(slice(int(a), int(b)) for a, b in zip(core_lo[k] - lo, core_hi[k] - lo))
+        if eng is None:
+            d_lab, label_bytes = host, host.dtype.itemsize
+            for L in table:
+                if span[0] <= L <= span[1]:
+                    words[place[L]] = L % (1 << 32)
+            if count:
+                values, found = np.unique(host[inner], return_counts=True)
+                for v, c in zip(values.tolist(), found.tolist()):
+                    if int(v) in place:
+                        counts[place[int(v)]] += c
+            return d_lab, label_bytes, words
+        d_flat, itemsize, _, ext, _, _ = _device_labels(eng, host)
+        d_lab, label_bytes, device_word = utility._narrow_labels(eng, d_flat, itemsize, span, table)
+        for L, w in device_word.items():
+            words[place[L]] = w
+        if count and device_word:
+            core = d_lab.view(ext[2], ext[1], ext[0])[inner[2], inner[1], inner[0]].reshape(-1)
+            found = utility._label_voxel_counts(eng, core, device_word.values())
+            for L, w in device_word.items():
+                counts[place[L]] += found[w]
+        return d_lab, label_bytes, words
+
+    def run_box(k, reach, vox, wrd, nrm, count):
+        """the sections (vox, wrd, nrm) in the box of core k at halo `reach` -> (area, contact, clip), None when it may not be loaded"""
+        lo, hi = np.maximum(core_lo[k] - reach, 0), np.minimum(core_hi[k] + reach, extent)
+        ext = tuple(int(v) for v in hi - lo)
+        if ext[0] * ext[1] * ext[2] > limit:
+            return None
+        t0 = time.perf_counter()
+        host = _load_box(dataset, lo, hi)
+        if host.shape != ext:
+            raise ValueError("cross_sectional_area_chunked: dataset[{}:{}] has shape {}".format(lo.tolist(), hi.tolist(), host.shape))
+        d_lab, label_bytes, words = box_labels(host, lo, k, count)
+        total["load_s"] += time.perf_counter() - t0
+        total["boxes_loaded"] += 1
+        total["voxels_loaded"] += ext[0] * ext[1] * ext[2]
+        want = words[wrd]
+        seed = section.seed_index(vox - lo, ext)
+        seed[want < 0] = section.OUTSIDE                                 # a label this box cannot hold
+        area, contact, clip, _ = run_sections(eng, d_lab, label_bytes, lo, ext, shape, an64, seed, np.maximum(want, 0).astype(np.uint32),
+                                              nrm, stats)
+        return area, contact, clip
+
+    def hook(vox, wrd, nrm):
+        cores = core_of(vox, shape, chunk_shape)
+
+        def launch(which):
+            which = np.asarray(which, dtype=np.int64)
+            area, contact = np.zeros(which.size, dtype=np.float32), np.zeros(which.size, dtype=np.uint8)
+            call = dict(boxes=[], items=[])
+            total["calls"].append(call)
+            pending, reach, grown = np.arange(which.size, dtype=np.int64), int(halo), 0
+            sweep = not state["counted"]                                 # the first launch visits every core, for the counts
+            while pending.size or sweep:
+                at = cores[which[pending]]
+                order = np.argsort(at, kind="stable")
+                ks, first = np.unique(at[order], return_index=True)
+                group = dict(zip(ks.tolist(), np.split(pending[order], first[1:])))
+                clipped, boxes = [none], 0
+                for k in (range(n_cores) if sweep else ks.tolist()):
+                    sel = group.get(k, none)
+                    got = run_box(k, reach, vox[which[sel]], wrd[which[sel]], nrm[which[sel]], sweep)
+                    if got is None:
+                        if grown == 0:
+                            raise ValueError("cross_sectional_area_chunked: the box of core {} at halo {} exceeds max_box_voxels = {}"
+                                             .format(k, reach, limit))
+                        contact[sel] |= XS_CLIPPED
+                        total["capped_items"] += int(sel.size)
+                        continue
+                    boxes += 1
+                    area[sel], contact[sel] = got[0], got[1]
+                    clipped.append(sel[got[2] != 0])
+                call["boxes"].append(boxes)
+                call["items"].append(int(pending.size))
+                total["items" if grown == 0 else "items_rerun"] += int(pending.size)
+                state["counted"], sweep = True, False
+                pending = np.sort(np.concatenate(clipped))
+                reach, grown = 2 * reach, grown + 1
+            return area, contact
+
+        return launch
+
+    if jobs:
+        utility._xs_run(None, None, None, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, launch_hook=hook)
+        if not state["counted"]:                                         # (no vertex lies on a path: the counts decide -1 or 0 all the same)
+            hook(np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.uint32), np.zeros((0, 3)))(none)
+        for (s, word, _), (area, contact) in zip(jobs, kept):           # utility.py:141-154, once the counts are known
+            if counts[word] < 2:
+                for name, value in (("cross_sectional_area", area), ("cross_sectional_area_contacts", contact)):
+                    if value is None:
+                        delattr(s, name)
+                    else:
+                        setattr(s, name, value)
+    utility._xs_finish(skels)
+    if timings is not None:
+        timings.update(total, kernel_ms=stats.get("kernel_ms", 0.0), rounds=stats.get("rounds", 0), vertices=stats.get("vertices", 0),
+                       occurrences=stats.get("occurrences", 0))
+    return skeletons
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -66,6 +66,25 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
     filled = (d_region, hole_begin, hole_count, d_hole_regions) selects kh_cross_sections_filled, the sections of filled(label):
     d_region u32 [nvox] on the device (kh_regions6 on d_lab), hole_begin / hole_count u32 [n] on the host (item i's holes are
     d_hole_regions[hole_begin[i] : hole_begin[i] + hole_count[i]], ascending region ids; hole_tables makes them per label)."""
+    return _sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, normals, stats, filled, None)
+
+
+def cross_sections_box(eng, d_lab, label_bytes, box_lo, box_shape, dataset_shape, anisotropy, seed_lin, want_label, normals, stats=None):
+    """cross_sections for a label array that is the box [box_lo, box_lo + box_shape) of a dataset of dataset_shape voxels, which may
+    hold 2^32 voxels or more (kh_cross_sections_box).  seed_lin: seed_index(voxel - box_lo, box_shape).  Returns host
+    arrays (area f32 [n], contact u8 [n], clip u8 [n], voxels u32 [n]): contact names the faces of the DATASET, clip, in the same bits,
+    the faces of the box that are cuts through the dataset.  An item with clip == 0 has the voxels, the contact and, bit for bit, the
+    area that cross_sections gives on the whole dataset: the fixed point is the dataset's (kh_cross_sections_fixed_exponent).  The
+    scratch is sized from the box: a small box gets small visited bitmaps and more concurrent waves.  stats as cross_sections."""
+    lo = tuple(int(v) for v in box_lo)
+    whole = tuple(int(v) for v in dataset_shape)
+    if len(lo) != 3 or len(whole) != 3:
+        raise ValueError("box_lo and dataset_shape have three entries")
+    return _sections(eng, d_lab, label_bytes, box_shape, anisotropy, seed_lin, want_label, normals, stats, None, (lo, whole))
+
+
+def _sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, normals, stats, filled, box):
+    """the body of cross_sections (box None: three arrays) and cross_sections_box (box = (box_lo, dataset_shape): four)"""
     t, P = eng.torch, eng.ptr
     sx, sy, sz = (int(v) for v in shape)
     an = np.asarray(anisotropy, dtype=np.float64).reshape(-1)
@@ -85,8 +104,16 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
             raise ValueError("region: one u32 per voxel (kh_regions6)")
         if n and int((hole_begin.astype(np.int64) + hole_count).max()) > int(d_hole_regions.numel()):
             raise ValueError("a hole range ends behind the region list")
+    if box is not None:
+        lo, whole = box
+        if any(o < 0 or o + b > d for o, b, d in zip(lo, (sx, sy, sz), whole)):
+            raise ValueError("the box %s + %s does not lie inside a dataset of shape %s" % (lo, (sx, sy, sz), whole))
+        exponent = int(eng.lib.kh_cross_sections_fixed_exponent(whole[0], whole[1], whole[2], float(an[0]), float(an[1]), float(an[2])))
+        if exponent == -2 ** 31:
+            raise ValueError("the extents of the dataset must lie in [1, 2^31)")
     if n == 0:
-        return np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32)
+        none = np.zeros(0, dtype=np.float32), np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint32)
+        return none if box is None else none[:2] + (np.zeros(0, dtype=np.uint8), none[2])
     if label_bytes not in (1, 2, 4):
         raise ValueError("labels of 1, 2 or 4 bytes (kimimaro_amd.utility._narrow_labels)")
     per_wave = int(eng.lib.kh_cross_sections_scratch_bytes(sx, sy, sz, 2)) - int(eng.lib.kh_cross_sections_scratch_bytes(sx, sy, sz, 1))
@@ -105,7 +132,12 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
         stream = t.cuda.current_stream(eng.device)
         before, after = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
         before.record(stream)
-    if filled is None:
+    if box is not None:
+        d_clip = eng.empty(n, t.uint8)
+        _abi.check(eng.lib.kh_cross_sections_box(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n, P(d_seed),
+                                                 P(d_want), P(d_normals), lo[0], lo[1], lo[2], whole[0], whole[1], whole[2], exponent,
+                                                 P(d_area), P(d_contact), P(d_voxels), P(d_clip), P(d_scratch), nbytes, eng.stream()))
+    elif filled is None:
         _abi.check(eng.lib.kh_cross_sections(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n, P(d_seed),
                                              P(d_want), P(d_normals), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
                                              eng.stream()))
@@ -127,4 +159,5 @@ def cross_sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_la
         stats["launches"] = stats.get("launches", 0) + 1
         stats["waves"] = waves
         stats["scratch_bytes"] = nbytes
-    return area, d_contact.cpu().numpy(), d_voxels.cpu().numpy().view(np.uint32)
+    contact, voxels = d_contact.cpu().numpy(), d_voxels.cpu().numpy().view(np.uint32)
+    return (area, contact, voxels) if box is None else (area, contact, d_clip.cpu().numpy(), voxels)

@@ -270,8 +270,14 @@ def _xs_occurrences(skel, an, offset, shape, smoothing_window, step):
     return vox, np.concatenate(occ_vertex), np.concatenate(occ_normal)
 
 
-def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, holes=None):
-    """holes (fill_holes=True): section.hole_tables' (d_region, word_range, d_hole_regions), handed to the launch of every round.
+def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, holes=None,
+            launch_hook=None):
+    """launch_hook (cross_sectional_area_chunked, kimimaro_amd.post): who evaluates the items when the volume is not resident.  Once
+    the items are laid out it is called as launch_hook(voxel int64 [m, 3], word u32 [m], normal f64 [m, 3]) -- item position k is
+    the section through `voxel[k]` (in the frame of `shape`, which may hold 2^32 voxels or more) of the job word `word[k]` with
+    `normal[k]` -- and returns the function from item positions (an int64 array) to (area f32, contact u8) that every round below
+    calls in place of section.cross_sections; eng, d_lab and label_bytes are not read then.
+    holes (fill_holes=True): section.hole_tables' (d_region, word_range, d_hole_regions), handed to the launch of every round.
     jobs: (skeleton, the device word of its label, the offset of the volume in the skeleton's voxel frame).  The sequential loop
     of the reference treats every vertex on its own -- a section depends on (voxel, normal, label) alone -- so its outcome is: a
     branch point is evaluated at every occurrence and ends as the mean; any other vertex is evaluated at its first occurrence when
@@ -280,6 +286,7 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
     t0 = time.perf_counter()
     an64 = an.astype(np.float64)
     starts, area_parts, contact_parts, seed_parts, word_parts, branch_parts, occ_v, occ_n = [0], [], [], [], [], [], [], []
+    vox_parts = []
     for skel, word, offset in jobs:
         nv = int(np.asarray(skel.vertices).reshape(-1, 3).shape[0])
         if repair_contacts or (multipass and hasattr(skel, "cross_sectional_area")):       # utility.py:250-255
@@ -290,7 +297,10 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
             area_parts.append(np.zeros(nv, dtype=np.float32))
             contact_parts.append(np.zeros(nv, dtype=np.uint8))
         vox, ov, on = _xs_occurrences(skel, an, offset, shape, smoothing_window, step)
-        seed_parts.append(section.seed_index(vox, shape))
+        if launch_hook is None:
+            seed_parts.append(section.seed_index(vox, shape))
+        else:
+            vox_parts.append(vox)
         word_parts.append(np.full(nv, word, dtype=np.uint32))
         is_branch = np.zeros(nv, dtype=bool)
         is_branch[skel.branches()] = True
@@ -324,10 +334,14 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
             ranges = np.array([word_range[int(w)] for w in uniq], dtype=np.uint32).reshape(-1, 2)
             hole_begin, hole_count = ranges[inverse, 0], ranges[inverse, 1]           # per vertex, as `words`
 
-        def launch(which):
+        def resident(which):
             filled = None if holes is None else (d_region, hole_begin[sv[which]], hole_count[sv[which]], d_hole_regions)
             return section.cross_sections(eng, d_lab, label_bytes, shape, an64, seeds[sv[which]], words[sv[which]], sn[which], stats,
                                           filled)[:2]
+
+        launch = resident
+        if launch_hook is not None:
+            launch = launch_hook(np.concatenate(vox_parts)[sv], words[sv], sn)
 
         t1 = time.perf_counter()
         open0 = (areas[sv] == 0) | ((contacts[sv] > 0) if repair_contacts else False)
@@ -438,14 +452,25 @@ def cross_sectional_area_filled(all_labels, skeletons, anisotropy=(1, 1, 1), smo
     return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, True, multipass, repair_contacts, step, _stats)
 
 
+def _xs_finish(skels):
+    """utility.py:551-558: both properties on every skeleton; -1 / 0 for one that was skipped and has no values yet"""
+    for s in skels:
+        _add_property(s, XS_PROP)
+        _add_property(s, XS_CONTACT_PROP)
+        if not hasattr(s, "cross_sectional_area"):
+            s.cross_sectional_area = np.full(len(s.vertices), -1, dtype=np.float32)
+        if not hasattr(s, "cross_sectional_area_contacts"):
+            s.cross_sectional_area_contacts = np.zeros(len(s.vertices), dtype=np.uint8)
+
+
 def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, multipass, repair_contacts, step, _stats):
     """the body of cross_sectional_area and cross_sectional_area_filled, after the argument checks"""
     eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
     skels = _skeleton_list(skeletons)
-    d_flat, itemsize, is_bool, shape, _, span = _device_labels(eng, all_labels)
-    if shape[0] * shape[1] * shape[2] >= 2 ** 32 - 1:
+    if int(np.prod([int(v) for v in getattr(all_labels, "shape", ())], dtype=object)) >= 2 ** 32 - 1:       # (before anything is copied)
         raise ValueError("the volume must hold fewer than 2^32 - 1 voxels")
+    d_flat, itemsize, is_bool, shape, _, span = _device_labels(eng, all_labels)
     labels_of = [_label_of(s, is_bool) for s in skels]
     d_lab, label_bytes, device_label = _narrow_labels(eng, d_flat, itemsize, span, {L for L in labels_of if L is not None})
     counts = _label_voxel_counts(eng, d_lab, device_label.values())
@@ -456,11 +481,5 @@ def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, 
         hole_stats = None if _stats is None else _stats.setdefault("holes", {})
         holes = section.hole_tables(eng, d_lab, label_bytes, shape, {word for _, word, _ in jobs}, hole_stats)
     _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats, holes)
-    for s in skels:                                                                        # utility.py:551-558
-        _add_property(s, XS_PROP)
-        _add_property(s, XS_CONTACT_PROP)
-        if not hasattr(s, "cross_sectional_area"):
-            s.cross_sectional_area = np.full(len(s.vertices), -1, dtype=np.float32)
-        if not hasattr(s, "cross_sectional_area_contacts"):
-            s.cross_sectional_area_contacts = np.zeros(len(s.vertices), dtype=np.uint8)
+    _xs_finish(skels)
     return skeletons
