@@ -545,8 +545,13 @@ __global__ __launch_bounds__(1024) void edf_batch_kernel(kh_label_t* tasks, int 
 // Nodes are 16-byte records {key bits, voxel, source index, -} in the label's slice of HBM scratch, so
 // a node is one dwordx4 load or store.  Keys are non-negative floats: they are compared as their bit
 // patterns (unsigned), which lets "ties go left" be written as k < sibling + (1 on left lanes).
-// A write-through LDS mirror of heap levels 0-12 was tried twice and measured 10-15 % SLOWER: the pop is
-// bound by instruction issue of its single wave more than by memory latency.
+// LDS mirrors, both ways.  A write-through mirror of WHOLE NODES of heap levels 0-12 was tried twice in the first rounds
+// (one volume alone) and measured 10-15 % slower: alone the pop's global trips hit the L2 and the pop is bound by the
+// instruction issue of its single wave.  The KEY mirror of levels 7-10 below is a different trade (4 bytes per slot, one
+// global trip less per pop).  Measured with twenty volumes in flight (BENCH_NOTES.md, "Heap key mirror"): bit exact, the longest
+// chain under load 11 789 -> 11 354 Mcyc (median of the lanes, -3.7 %), the step time 370.1 -> 368.4 ms (medians of three, the
+// parent's own spread 13.6 ms): NOT a gain beyond the spread -- the trip it removes is not what doubles the chain under load.
+// No new spills in invalidate_ball, +57 instructions.  -DKH_HEAP_MIRROR_LEVELS=0 is the code without it.
 // a native LLVM vector (HIP's uint4 is a struct around a union, which ends up in scratch memory here)
 typedef uint32_t hnode_t __attribute__((ext_vector_type(4)));
 // LDS pointers keep their address space in the type, so LDS and HBM accesses can never be merged into flat_* ones
@@ -557,13 +562,35 @@ typedef __attribute__((address_space(3))) hnode_t lds_hnode_t;
 // TOPL = 2: two chunks (8191 slots, 128 KiB): one such workgroup fits on a CU, so it is reserved for the few
 // largest labels, whose sequential chain is the critical path of the whole launch.  Every pop starts in the
 // LDS part, so the top read and the first TOPL chunks cost LDS round trips instead of L2 ones.
+//
+// The key mirror (TOPL = 1 only).  Behind the 130 LDS nodes lie the KEYS of the next KH_HEAP_MIRROR_LEVELS heap levels (default 4:
+// levels 7-10, slots 127..2046, 7 680 B).  The nodes of those slots stay in HBM and HBM is the truth; every store to such a slot
+// writes its key through (heap_store, the pop's moves).  A pop decides its path through those levels from the keys alone and
+// fetches the (at most 4) whole nodes on it together with the 6 levels under them: a heap below 131 072 nodes costs a pop one
+// global round trip instead of two.  The mirror is never initialised: a slot is read only below `len`, and it was written when
+// it was filled.  The bytes are the workgroup's dynamic LDS, which the sweep and the searches use between the heap's calls.
+// 0 compiles the stage out.
+#ifndef KH_HEAP_MIRROR_LEVELS
+#define KH_HEAP_MIRROR_LEVELS 4
+#endif
+static_assert(KH_HEAP_MIRROR_LEVELS >= 0 && KH_HEAP_MIRROR_LEVELS <= 5, "the mirror stage resolves at most 62 nodes (one per lane)");
+typedef __attribute__((address_space(3))) uint32_t lds_key_t;
+
 template <int TOPL_>
 struct Heap {
   static constexpr int TOPL = TOPL_;
   static constexpr uint32_t TOP = TOPL_ == 1 ? 127u : 8191u;
+  static constexpr int MIRL = TOPL_ == 1 ? KH_HEAP_MIRROR_LEVELS : 0;     // mirrored levels under the LDS part
+  static constexpr uint32_t MIR_END = ((TOP + 1u) << MIRL) - 1u;          // slots TOP .. MIR_END-1 have their key in LDS too
+  static constexpr size_t LDS_BYTES = (size_t)(TOP + 3u) * 16u + (size_t)(MIR_END - TOP) * 4u;
+  // pop: nested 6-level chunks (the LDS ones included).  32-bit index math needs every hole at level <= 24:
+  // without the mirror the holes sit at levels 0, 6, .., 24 (30 levels), with it at 0, 6 | 6+MIRL, .., 18+MIRL (<= 29 levels)
+  static constexpr int CHUNKS = MIRL ? 4 : 5;
+  static constexpr uint32_t MAX_N = MIRL ? (1u << (6 * CHUNKS + MIRL + 1)) - 1u : 0x7FFFFFFFu;   // the nodes a pop can descend through
   hnode_t* node;   // HBM scratch of this label (L2 resident in practice); slots < TOP unused
-  lds_hnode_t* top;  // LDS, TOP + 3 entries (the last LDS chunk's lanes 62/63 read two slots past the end)
+  lds_hnode_t* top;  // LDS, TOP + 3 entries (the last LDS chunk's lanes 62/63 read two slots past the end); then the key mirror
   uint32_t cap, n;
+  __device__ __forceinline__ lds_key_t* mir() const { return (lds_key_t*)(top + (TOP + 3u)); }   // key of slot i: mir()[i - TOP]
   // per-lane constants of the 126-node speculative sub-tree (children of node m: 2m+2, 2m+3; parent of
   // m >= 2: (m-2)>>1).  Lane l holds node m = l ("slot 0", depths 1..6) and m = l+64 ("slot 1", depth 6).
   unsigned long long am0, am1;  // slot-0 ballot bits of the node's ancestors (am0 including itself)
@@ -589,6 +616,16 @@ __device__ __forceinline__ void heap_init_lane(H& h, int lane) {
   h.j0 = (uint32_t)(lane + 2 - (1 << d0));
   h.j1 = (uint32_t)(lane + 2);
   h.lf = (lane & 1) ? 0u : 1u;
+}
+
+// store of a whole node to slot i, wherever it lives (the mirror's key written through)
+template <class H>
+__device__ __forceinline__ void heap_store(const H& h, uint32_t i, hnode_t v) {
+  if (i < H::TOP) h.top[i] = v;
+  else {
+    h.node[i] = v;
+    if constexpr (H::MIRL > 0) { if (i < H::MIR_END) h.mir()[i - H::TOP] = v.x; }
+  }
 }
 
 // all 64 lanes of the wave call this with uniform arguments.  One memory round trip: lane g loads
@@ -618,10 +655,7 @@ __device__ __forceinline__ bool heap_push_wave(H& h, uint32_t kbits, uint32_t vo
   const uint32_t dest = ((pos + 1u) >> (lane < 31 ? lane : 31)) - 1u;  // slot of generation `lane` (lane 0: the new leaf)
   const hnode_t fresh = {kbits, vox, src, 0u};
   const hnode_t val = lane < m ? a : fresh;
-  if (lane <= m) {
-    if (dest < H::TOP) h.top[dest] = val;
-    else h.node[dest] = val;
-  }
+  if (lane <= m) heap_store(h, dest, val);
   return true;
 }
 
@@ -635,7 +669,10 @@ __device__ __forceinline__ bool heap_push_wave(H& h, uint32_t kbits, uint32_t vo
 // load of `last` overlaps the whole descent.  Loads are unconditional (index clamped, key masked
 // to +inf): no divergent branches in the descent.  Chunk 0 is exactly the LDS part of the heap.
 // 32-bit index math is safe: the hole of chunk c sits at level 6c <= 24, so (hole+1) << 6 < 2^31.
-#define KH_POP_CHUNKS 5  /* 5 * 6 = 30 levels */
+// With the key mirror (H::MIRL > 0) the keys-only stage heap_pop_mirror sits between the LDS part and the first global chunk.
+template <int C, class H>
+__device__ __forceinline__ void heap_pop_mirror(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
+                                                uint32_t& deepest, bool& found);
 template <int C, class H>
 __device__ __forceinline__ void heap_pop_chunk(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
                                                uint32_t& deepest, bool& found) {
@@ -653,13 +690,16 @@ __device__ __forceinline__ void heap_pop_chunk(const H& h, uint32_t hole, uint32
   const unsigned long long W0 = ballot64(w0);
   const bool on0 = (W0 & h.am0) == h.am0;
   const bool on1 = w1 && ((W0 & h.am1) == h.am1);
-  if constexpr (C + 1 < KH_POP_CHUNKS) {
+  if constexpr (C + 1 < H::CHUNKS) {
     // next hole = the depth-6 node of the path, if the path got that deep and that node has children
     const unsigned long long P0 = ballot64(on0), P1 = ballot64(on1);
     uint32_t nh = 0;
     if (P1) nh = rdlane_u32(i1, __ffsll((long long)P1) - 1);
     else if (P0 >> 62) nh = rdlane_u32(i0, (P0 >> 63) ? 63 : 62);
-    if (nh != 0u && 2u * nh + 1u < len) heap_pop_chunk<C + 1, H>(h, nh, len, vk, lane, deepest, found);
+    if (nh != 0u && 2u * nh + 1u < len) {
+      if constexpr (H::MIRL > 0 && C + 1 == H::TOPL) heap_pop_mirror<C + 1, H>(h, nh, len, vk, lane, deepest, found);
+      else heap_pop_chunk<C + 1, H>(h, nh, len, vk, lane, deepest, found);
+    }
   }
   // every path node with key < last.key moves to its parent's slot; `last` lands in the slot of the
   // deepest such node (or the root).  Path keys are non-decreasing with depth.
@@ -669,6 +709,10 @@ __device__ __forceinline__ void heap_pop_chunk(const H& h, uint32_t hole, uint32
   if constexpr (C < H::TOPL) {
     if (mv0) h.top[q0] = n0;
     if (mv1) h.top[q1] = n1;
+  } else if constexpr (C == H::TOPL && H::MIRL > 0) {
+    // the parent of this chunk's two depth-1 nodes (lanes 0, 1) is the hole: a slot of the deepest mirrored level
+    if (mv0) { h.node[q0] = n0; if (lane < 2) h.mir()[hole - H::TOP] = k0; }
+    if (mv1) h.node[q1] = n1;
   } else if constexpr (C == H::TOPL) {
     // the parent of this chunk's two depth-1 nodes (lanes 0, 1) is the hole: a leaf of the LDS part
     if (mv0) { if (lane < 2) h.top[hole] = n0; else h.node[q0] = n0; }
@@ -684,6 +728,41 @@ __device__ __forceinline__ void heap_pop_chunk(const H& h, uint32_t hole, uint32
   }
 }
 
+// The keys-only stage under the hole at the last LDS level: the speculative sub-tree of MIRL levels is 2^(MIRL+1) - 2 slots (30),
+// lane l holds its node l exactly as in a chunk's slot 0.  The key comes from the mirror; sibling compare, ballot and ancestor
+// masks are the chunk's.  Then the lanes on the path fetch their whole node from HBM (the moves need {voxel, source}) -- every
+// lane loads, the others the clamp slot -- and the first global chunk starts under the hole at the deepest mirrored level: both
+// are in flight together, one round trip.  Writes on the way back up, as in a chunk.
+template <int C, class H>
+__device__ __forceinline__ void heap_pop_mirror(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
+                                                uint32_t& deepest, bool& found) {
+  constexpr int NN = (2 << H::MIRL) - 2;           // nodes of the sub-tree
+  constexpr int D0 = (1 << H::MIRL) - 2;           // its first node of the deepest level
+  const uint32_t i0 = ((hole + 1u) << h.sh0) - 1u + h.j0;
+  const bool e0 = (lane < NN) && (i0 < len);
+  const uint32_t km = h.mir()[e0 ? i0 - H::TOP : 0u];
+  const uint32_t k0 = e0 ? km : INF_BITS;
+  const bool w0 = e0 & (k0 < sibling_u32(k0) + h.lf);
+  const unsigned long long W0 = ballot64(w0);
+  const bool on0 = (W0 & h.am0) == h.am0;
+  const hnode_t n0 = h.node[on0 ? i0 : H::TOP];
+  {
+    const unsigned long long PD = ballot64(on0) >> D0;
+    const uint32_t nh = PD ? rdlane_u32(i0, D0 + __ffsll((long long)PD) - 1) : 0u;
+    if (nh != 0u && 2u * nh + 1u < len) heap_pop_chunk<C, H>(h, nh, len, vk, lane, deepest, found);
+  }
+  const bool mv0 = on0 && k0 < vk;
+  const uint32_t q0 = (i0 - 1u) >> 1;
+  if (mv0) {
+    if (lane < 2) h.top[hole] = n0;      // the hole is a leaf of the LDS part
+    else { h.node[q0] = n0; h.mir()[q0 - H::TOP] = k0; }
+  }
+  if (!found) {
+    const unsigned long long M0 = ballot64(mv0);
+    if (M0) { deepest = rdlane_u32(i0, 63 - __clzll((long long)M0)); found = true; }
+  }
+}
+
 template <class H>
 __device__ __forceinline__ void heap_pop_wave(H& h, int lane) {
   const uint32_t len = h.n - 1u;
@@ -693,10 +772,7 @@ __device__ __forceinline__ void heap_pop_wave(H& h, int lane) {
   uint32_t deepest = 0;
   bool found = false;
   if (len > 1u) heap_pop_chunk<0, H>(h, 0u, len, last.x, lane, deepest, found);
-  if (lane == 0) {
-    if (deepest < H::TOP) h.top[deepest] = last;
-    else h.node[deepest] = last;
-  }
+  if (lane == 0) heap_store(h, deepest, last);
 }
 
 // wave 0 only.  Returns the number of voxels invalidated.  PROF adds the pop / push / neighbour-test
@@ -805,8 +881,7 @@ __device__ __attribute__((noinline)) uint32_t invalidate_ball(const Geometry& g,
       const unsigned long long run = c < 64 ? (m & ((1ull << c) - 1ull)) : m;
       if ((run >> lane) & 1ull) {
         const hnode_t fresh = {ndb, q, si, 0u};
-        if (leaf < H::TOP) h.top[leaf] = fresh;
-        else h.node[leaf] = fresh;
+        heap_store(h, leaf, fresh);
       }
       const uint32_t nrun = (uint32_t)__popcll(run);
       h.n = base + nrun;
@@ -1164,7 +1239,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   __shared__ Sweep sw;
   __shared__ SweepShared swsh;
   __shared__ uint32_t sweep_stats[5];
-  // (Heap<TOPL>::TOP + 3) nodes for the heap emulation; the sweep's level words and lists use the same bytes
+  // Heap<TOPL>::LDS_BYTES for the heap emulation (TOP + 3 nodes, the key mirror); the sweep's level words and lists use the same bytes
   extern __shared__ __attribute__((aligned(16))) unsigned char heap_top[];
   kh_label_t* task = &tasks[blockIdx.x];
   const int tid = threadIdx.x;
@@ -1183,7 +1258,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   hnode_t* const pool = (ghost_mode & 8u) ? heap_nodes : nullptr;      // KH_TRACE_SCRATCH_POOL: heap and journal on demand
   heap.node = pool ? nullptr : heap_nodes + task->heap_offset;
   heap.top = (lds_hnode_t*)heap_top;
-  heap.cap = task->heap_capacity;
+  heap.cap = task->heap_capacity < Heap<TOPL>::MAX_N ? task->heap_capacity : Heap<TOPL>::MAX_N;   // beyond: KH_ST_HEAP_OVERFLOW
   heap.n = 0;
   heap_init_lane(heap, lane);
   uint32_t* pverts = path_vertices + task->path_offset;
@@ -1528,7 +1603,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void invalidate_ball_ke
   Heap<1> heap;
   heap.node = heap_nodes + task->heap_offset;
   heap.top = (lds_hnode_t*)heap_top;
-  heap.cap = task->heap_capacity;
+  heap.cap = task->heap_capacity < Heap<1>::MAX_N ? task->heap_capacity : Heap<1>::MAX_N;
   heap.n = 0;
   heap_init_lane(heap, lane);
   if (tid == 0) {
@@ -1804,7 +1879,7 @@ static int launch_trace(int count, hipStream_t st, kh_label_t* tasks, const uint
                         int fix_branching, const SweepGlobal& sg, uint32_t max_nlev, unsigned nthreads, uint32_t* journal,
                         float* rail_save, uint32_t ghost_mode, const uint8_t* corner_gate) {
   if (count <= 0) return KH_OK;
-  size_t lds = (size_t)(Heap<TOPL>::TOP + 3) * sizeof(hnode_t);
+  size_t lds = Heap<TOPL>::LDS_BYTES;          // the heap's LDS part (and key mirror)
   const size_t swl = sweep_lds_bytes(max_nlev);
   if (sg.on && swl > lds) lds = swl;
   if ((size_t)KH_SSSP_LDS_BYTES * nthreads > lds) lds = (size_t)KH_SSSP_LDS_BYTES * nthreads;     // the searches' scratch (same bytes)
@@ -1914,7 +1989,7 @@ extern "C" int kh_invalidate_ball(kh_label_t* task, const uint32_t* lists, const
     set_error("kh_invalidate_ball: sweep arguments (level table or integer-mode factors, cstate, sched, a 256-byte aligned event arena, max_nlev)");
     return KH_EINVAL;
   }
-  size_t lds = (size_t)(Heap<1>::TOP + 3) * sizeof(hnode_t);
+  size_t lds = Heap<1>::LDS_BYTES;
   const size_t swl = sweep_lds_bytes((uint32_t)max_nlev);
   if (sg.on && swl > lds) lds = swl;
   {
