@@ -417,7 +417,16 @@ int kh_fill_voids_nd(const uint8_t* mask, int ndim, int64_t sx, int64_t sy, int6
  *   unordered pairs of regions that share a voxel face, key = smaller id << 32 | larger id, 0 = empty slot, in no particular order;
  *   state (device u32 [2], set by the call): [0] = keys in the table, [1] != 0: the table was too small and holds a PART of the
  *   set -- call again with a larger one (memory is bounded by the capacity, not by the number of faces).
- * kh_region_apply: labels[v] = owner[region[v]] where that is non-zero (owner: u64 [R + 1]), in place.                          */
+ * kh_region_apply: labels[v] = owner[region[v]] where that is non-zero (owner: u64 [R + 1]), in place.
+ * kh_region_table_box: kh_region_table for a label array that is a box of a dataset.  dataset_faces names the faces
+ *   of the array that are faces of the DATASET (bit 0 x == 0, bit 1 x == sx-1, bits 2, 3 the y faces, 4, 5 the z faces; what
+ *   kh_cross_sections_box derives from o, b and d): face = 1 iff the region owns a voxel on one of those.  value and count are
+ *   kh_region_table's; dataset_faces == 63 gives its face flags too, 0 gives none.  More than six bits are a bad argument.
+ * kh_region_seam_pairs: low, high (u32 [m], 1 <= m < 2^32) are two planes of region ids that face each other across
+ *   a cut, low[p] the neighbour of high[p]; the distinct keys low[p] << 32 | high[p] are put into `table` with kh_region_pairs'
+ *   layout, capacity rule, `state` and overflow report (call again with a larger table).  The caller numbers the regions so that
+ *   low[p] < high[p]; no labels are read: whether a pair joins two pieces of one region (equal value) or two adjacent regions is
+ *   the caller's to tell.                                                                                                        */
 int kh_regions6(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint32_t* chunk_counts,
                 uint32_t* region, uint32_t* representative, uint32_t* nregions, void* stream);
 int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative, int64_t nregions,
@@ -425,6 +434,11 @@ int kh_region_table(const void* labels, int label_bytes, const uint32_t* region,
 int kh_region_pairs(const uint32_t* region, int64_t sx, int64_t sy, int64_t sz, uint64_t* table, int64_t capacity, uint32_t* state,
                     void* stream);
 int kh_region_apply(const uint32_t* region, const uint64_t* owner, void* labels, int label_bytes, int64_t nvox, void* stream);
+int kh_region_table_box(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative, int64_t nregions,
+                        int ndim, int64_t sx, int64_t sy, int64_t sz, uint32_t dataset_faces, uint64_t* value, uint32_t* count,
+                        uint8_t* face, void* stream);
+int kh_region_seam_pairs(const uint32_t* low, const uint32_t* high, int64_t m, uint64_t* table, int64_t capacity, uint32_t* state,
+                         void* stream);
 /* host (no GPU needed): who fills what, on the region graph.  value / count / face: the table of kh_region_table ([nregions + 1]);
  * pairs: u64 [npairs], the non-empty keys of kh_region_pairs in any order, each unordered pair once.  The labels (non-zero values,
  * compared as unsigned words) are gone through in ascending order with a dead set, as the reference's loop does:
@@ -553,7 +567,12 @@ int kh_cross_sections_filled(const void* labels, int label_bytes, int64_t sx, in
  * integer sum of a section with clip == 0 the one kh_cross_sections computes on the whole dataset, and area bit-equal.  It must not
  * be smaller than the box's own exponent (bad argument), which keeps every sum below 2^62.
  * scratch: kh_cross_sections_scratch_bytes of the BOX's extents.  Everything else as kh_cross_sections; clip is 0 for an empty
- * section.  There is no filled variant.
+ * section.
+ * kh_cross_sections_filled_box: both at once, kh_cross_sections_box's arguments and kh_cross_sections_filled's
+ * region / hole_begin / hole_count / hole_regions.  region (u32 [sx * sy * sz]) holds, for the voxels of the box, region ids of the
+ * DATASET's region graph in any numbering the lists share (kimimaro_amd.post.region_graph_chunked's provisional ids); an item's list
+ * names, ascending, the regions of hole(label) taken on the dataset that have voxels in the box.  An item with hole_count 0 gives
+ * kh_cross_sections_box's outputs bit for bit, an item with clip == 0 what kh_cross_sections_filled gives on the whole dataset.
  * kh_cross_sections_fixed_exponent (host, no device needed): the e kh_cross_sections uses for a volume of extents (dx, dy, dz), each
  * below 2^31, with the anisotropy (ax, ay, az): the binary exponent of ((ax*ay + ay*az) + ax*az) * min(4 * largest face, dx*dy*dz),
  * the face exact in 64 bits, the other products float64.  INT32_MIN for extents or an anisotropy the launches refuse, or a
@@ -562,6 +581,12 @@ int kh_cross_sections_box(const void* labels, int label_bytes, int64_t sx, int64
                           int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals, int64_t ox,
                           int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz, int fixed_exponent, float* area,
                           uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch, int64_t scratch_bytes, void* stream);
+int kh_cross_sections_filled_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                                 double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                 const double* normals, const uint32_t* region, const uint32_t* hole_begin, const uint32_t* hole_count,
+                                 const uint32_t* hole_regions, int64_t ox, int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz,
+                                 int fixed_exponent, float* area, uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch,
+                                 int64_t scratch_bytes, void* stream);
 int kh_cross_sections_fixed_exponent(int64_t dx, int64_t dy, int64_t dz, double ax, double ay, double az);
 /* host: the membership test and the area of ONE voxel at offset (dx, dy, dz) from the seed, by the functions the kernel runs
  * (normal, anisotropy: f64 [3]).  Returns 1 if the voxel is cut; *offset = d, *half_width = h, *area = area(plane /\ box).      */

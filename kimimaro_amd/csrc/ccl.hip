@@ -546,9 +546,11 @@ __global__ __launch_bounds__(256) void reg_value_kernel(const LT* __restrict__ l
 }
 
 // lanes along x: the first lane of a run of equal region ids inside its 64-lane chunk adds the run's length and sets the face flag
-// for the whole run (one atomic per run, not per voxel; the flag is looked at before it is written)
+// for the whole run (one atomic per run, not per voxel; the flag is looked at before it is written).  faces: which faces of the array
+// count (bit 0 x == 0, bit 1 x == sx-1, bits 2, 3 the y faces, 4, 5 the z faces); kh_region_table passes all six, kh_region_table_box
+// those of a box that are faces of its dataset (XsBox::dataset_faces of section.hip)
 __global__ __launch_bounds__(256) void reg_table_kernel(const uint32_t* __restrict__ region, int sx, int sy, int sz, int ndim,
-                                                        uint32_t* __restrict__ count, uint8_t* face) {
+                                                        uint32_t faces, uint32_t* __restrict__ count, uint8_t* face) {
   const int xt = (sx + 255) >> 8;
   const int64_t ntiles = (int64_t)xt * sy * sz;
   const int lane = threadIdx.x & 63;
@@ -567,7 +569,10 @@ __global__ __launch_bounds__(256) void reg_table_kernel(const uint32_t* __restri
       const int end = later ? __builtin_ctzll(later) : nvalid;
       const int len = end - lane;
       atomicAdd(&count[r], (uint32_t)len);
-      const bool f = x == 0 || x + len == sx || (ndim >= 2 && (y == 0 || y == sy - 1)) || (ndim >= 3 && (z == 0 || z == sz - 1));
+      const uint32_t on = (x == 0 ? 1u : 0u) | (x + len == sx ? 2u : 0u) |
+                          (ndim >= 2 ? (y == 0 ? 4u : 0u) | (y == sy - 1 ? 8u : 0u) : 0u) |
+                          (ndim >= 3 ? (z == 0 ? 16u : 0u) | (z == sz - 1 ? 32u : 0u) : 0u);
+      const bool f = (on & faces) != 0u;
       if (f && face[r] == 0) face[r] = 1;
     }
   }
@@ -623,6 +628,23 @@ __global__ __launch_bounds__(256) void reg_pairs_kernel(const uint32_t* __restri
   }
 }
 
+// seam pairs: two facing planes of region ids on either side of a cut through a dataset, low[p] facing high[p]; the
+// keys low[p] << 32 | high[p] go into the set above by the same insert.  The caller numbers the regions so that the low side has the
+// smaller ids; the kernel reads no labels and does not ask whether the two regions carry one value.
+__global__ __launch_bounds__(256) void reg_seam_pairs_kernel(const uint32_t* __restrict__ low, const uint32_t* __restrict__ high, int64_t m,
+                                                             unsigned long long* table, unsigned long long mask, uint32_t* state) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ntiles = (m + 255) >> 8;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    if (__shfl(__hip_atomic_load(&state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0) != 0u) return;
+    const int64_t p = t * 256 + threadIdx.x;
+    unsigned long long key = p < m ? (((unsigned long long)low[p] << 32) | (unsigned long long)high[p]) : 0ull;
+    const unsigned long long before = __shfl_up(key, 1);
+    if (lane > 0 && before == key) key = 0ull;
+    if (key != 0ull) reg_pair_insert(table, mask, key, state);
+  }
+}
+
 // apply: a voxel of a region with an owner takes the owner's value
 template <typename LT>
 __global__ __launch_bounds__(256) void reg_apply_kernel(const uint32_t* __restrict__ region, const unsigned long long* __restrict__ owner,
@@ -658,28 +680,46 @@ extern "C" int kh_regions6(const void* labels, int label_bytes, int64_t sx, int6
   return KH_OK;
 }
 
-extern "C" int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative,
-                               int64_t nregions, int ndim, int64_t sx, int64_t sy, int64_t sz, uint64_t* value, uint32_t* count,
-                               uint8_t* face, void* stream) {
+static int region_table_impl(const char* name, const void* labels, int label_bytes, const uint32_t* region,
+                             const uint32_t* representative, int64_t nregions, int ndim, int64_t sx, int64_t sy, int64_t sz,
+                             uint32_t faces, uint64_t* value, uint32_t* count, uint8_t* face, void* stream) {
   if (int rc = kh::require_device()) return rc;
   if (!labels || !region || !representative || !value || !count || !face || sx <= 0 || sy <= 0 || sz <= 0 || sx >= (1ll << 31) ||
       sy >= (1ll << 31) || sz >= (1ll << 31) || sx * sy * sz >= (1ll << 32) - 1 || nregions < 1 || nregions > sx * sy * sz ||
       ndim < 1 || ndim > 3 || (ndim < 3 && sz != 1) || (ndim < 2 && sy != 1)) {
-    kh::set_error("kh_region_table: bad arguments (null pointer, empty volume, >= 2^32-1 voxels, nregions outside [1, nvox], or an "
-                  "axis beyond ndim with extent > 1)");
+    kh::set_error("%s: bad arguments (null pointer, empty volume, >= 2^32-1 voxels, nregions outside [1, nvox], or an "
+                  "axis beyond ndim with extent > 1)", name);
+    return KH_EINVAL;
+  }
+  if (faces > 63u) {
+    kh::set_error("%s: dataset_faces has six bits", name);
     return KH_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
   KH_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(uint32_t) * (size_t)(nregions + 1), st));
   KH_HIP_CHECK(hipMemsetAsync(face, 0, (size_t)(nregions + 1), st));
-  KH_REG_DISPATCH(label_bytes, "kh_region_table",
+  KH_REG_DISPATCH(label_bytes, "kh_region_table",      // (the message serves both entries: the argument is the same)
                   hipLaunchKernelGGL((kh::reg_value_kernel<LT>), dim3(kh::ccl_grid(nregions + 1, 256)), dim3(256), 0, st,
                                      (const LT*)labels, representative, nregions, (unsigned long long*)value));
   const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
   hipLaunchKernelGGL(kh::reg_table_kernel, dim3(kh::ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, region, (int)sx, (int)sy, (int)sz,
-                     ndim, count, face);
+                     ndim, faces, count, face);
   KH_LAUNCH_CHECK();
   return KH_OK;
+}
+
+extern "C" int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative,
+                               int64_t nregions, int ndim, int64_t sx, int64_t sy, int64_t sz, uint64_t* value, uint32_t* count,
+                               uint8_t* face, void* stream) {
+  return region_table_impl("kh_region_table", labels, label_bytes, region, representative, nregions, ndim, sx, sy, sz, 63u, value, count,
+                           face, stream);
+}
+
+extern "C" int kh_region_table_box(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative,
+                                   int64_t nregions, int ndim, int64_t sx, int64_t sy, int64_t sz, uint32_t dataset_faces,
+                                   uint64_t* value, uint32_t* count, uint8_t* face, void* stream) {
+  return region_table_impl("kh_region_table_box", labels, label_bytes, region, representative, nregions, ndim, sx, sy, sz, dataset_faces,
+                           value, count, face, stream);
 }
 
 extern "C" int kh_region_pairs(const uint32_t* region, int64_t sx, int64_t sy, int64_t sz, uint64_t* table, int64_t capacity,
@@ -696,6 +736,22 @@ extern "C" int kh_region_pairs(const uint32_t* region, int64_t sx, int64_t sy, i
   KH_HIP_CHECK(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), st));
   const int64_t ntiles = ((sx + 255) / 256) * sy * sz;
   hipLaunchKernelGGL(kh::reg_pairs_kernel, dim3(kh::ccl_grid(ntiles, 1, 1 << 20)), dim3(256), 0, st, region, (int)sx, (int)sy, (int)sz,
+                     (unsigned long long*)table, (unsigned long long)(capacity - 1), state);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_region_seam_pairs(const uint32_t* low, const uint32_t* high, int64_t m, uint64_t* table, int64_t capacity,
+                                    uint32_t* state, void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!low || !high || !table || !state || m <= 0 || m >= (1ll << 32) || capacity < 64 || (capacity & (capacity - 1)) != 0) {
+    kh::set_error("kh_region_seam_pairs: bad arguments (null pointer, m outside [1, 2^32), or a capacity that is no power of two >= 64)");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_HIP_CHECK(hipMemsetAsync(table, 0, sizeof(uint64_t) * (size_t)capacity, st));
+  KH_HIP_CHECK(hipMemsetAsync(state, 0, 2 * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(kh::reg_seam_pairs_kernel, dim3(kh::ccl_grid((m + 255) / 256, 1, 1 << 20)), dim3(256), 0, st, low, high, m,
                      (unsigned long long*)table, (unsigned long long)(capacity - 1), state);
   KH_LAUNCH_CHECK();
   return KH_OK;

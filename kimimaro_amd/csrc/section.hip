@@ -28,6 +28,9 @@
 // the epilogue splits the one accumulator by a mask: contact = touch & dataset_faces, clip = touch & ~dataset_faces.  The fixed
 // point's quantum comes from the caller (the dataset's, kh_cross_sections_fixed_exponent), so that a section no cut clips sums to
 // the same integer in every box and in the whole dataset.
+//
+// FILLED && BOX (kh_cross_sections_filled_box) is both at once and adds no statement: the region ids are those of
+// the DATASET's region graph (the box of the region store), the lists name the dataset's hole regions that have voxels in the box.
 #include <math.h>
 
 #include "common.h"
@@ -367,7 +370,8 @@ extern "C" int64_t kh_cross_sections_scratch_bytes(int64_t sx, int64_t sy, int64
   return XS_HEADER_BYTES + n_waves * L.wave_bytes;
 }
 
-// all entry points: hs == nullptr && bx == nullptr launches the plain instantiation, `name` heads the error messages;
+// all entry points: hs == nullptr && bx == nullptr launches the plain instantiation, both given the filled box one; `name` heads the
+// error messages;
 // fixed_exponent is read with bx alone
 static int xs_launch(const char* name, const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
                      double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals,
@@ -435,7 +439,10 @@ static int xs_launch(const char* name, const void* labels, int label_bytes, int6
   const XsBox whole = {63u, nullptr};
 #define KH_XS_LAUNCH(LT)                                                                                                              \
   do {                                                                                                                                \
-    if (hs) hipLaunchKernelGGL((cross_sections_kernel<LT, true, false>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs, whole);  \
+    if (hs && bx) hipLaunchKernelGGL((cross_sections_kernel<LT, true, true>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs,    \
+                                     *bx);                                                                                            \
+    else if (hs) hipLaunchKernelGGL((cross_sections_kernel<LT, true, false>), dim3(grid), block, 0, st, (const LT*)labels, p, *hs,    \
+                                    whole);                                                                                           \
     else if (bx) hipLaunchKernelGGL((cross_sections_kernel<LT, false, true>), dim3(grid), block, 0, st, (const LT*)labels, p, none,    \
                                     *bx);                                                                                             \
     else hipLaunchKernelGGL((cross_sections_kernel<LT, false, false>), dim3(grid), block, 0, st, (const LT*)labels, p, none, whole);   \
@@ -469,12 +476,12 @@ extern "C" int kh_cross_sections_filled(const void* labels, int label_bytes, int
                    nullptr, 0, area, contact, voxels, scratch, scratch_bytes, stream);
 }
 
-extern "C" int kh_cross_sections_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
-                                     double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
-                                     const double* normals, int64_t ox, int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz,
-                                     int fixed_exponent, float* area, uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch,
-                                     int64_t scratch_bytes, void* stream) {
-  const char* name = "kh_cross_sections_box";
+// the two box entries: hs == nullptr is kh_cross_sections_box
+static int xs_launch_box(const char* name, const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                         double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label, const double* normals,
+                         const XsHoles* hs, int64_t ox, int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz, int fixed_exponent,
+                         float* area, uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch, int64_t scratch_bytes,
+                         void* stream) {
   if (ox < 0 || oy < 0 || oz < 0 || sx <= 0 || sy <= 0 || sz <= 0 || dx <= 0 || dy <= 0 || dz <= 0 || ox > dx - sx || oy > dy - sy ||
       oz > dz - sz) {
     set_error("%s: the box [o, o + b) must lie inside the dataset [0, d)", name);
@@ -488,8 +495,29 @@ extern "C" int kh_cross_sections_box(const void* labels, int label_bytes, int64_
   bx.dataset_faces = (ox == 0 ? 1u : 0u) | (ox + sx == dx ? 2u : 0u) | (oy == 0 ? 4u : 0u) | (oy + sy == dy ? 8u : 0u) |
                      (oz == 0 ? 16u : 0u) | (oz + sz == dz ? 32u : 0u);
   bx.clip = clip;
-  return xs_launch(name, labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, nullptr, &bx,
+  return xs_launch(name, labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals, hs, &bx,
                    fixed_exponent, area, contact, voxels, scratch, scratch_bytes, stream);
+}
+
+extern "C" int kh_cross_sections_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax, double ay,
+                                     double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                     const double* normals, int64_t ox, int64_t oy, int64_t oz, int64_t dx, int64_t dy, int64_t dz,
+                                     int fixed_exponent, float* area, uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch,
+                                     int64_t scratch_bytes, void* stream) {
+  return xs_launch_box("kh_cross_sections_box", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label, normals,
+                       nullptr, ox, oy, oz, dx, dy, dz, fixed_exponent, area, contact, voxels, clip, scratch, scratch_bytes, stream);
+}
+
+extern "C" int kh_cross_sections_filled_box(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, double ax,
+                                            double ay, double az, int64_t n_items, const uint32_t* seed_lin, const uint32_t* want_label,
+                                            const double* normals, const uint32_t* region, const uint32_t* hole_begin,
+                                            const uint32_t* hole_count, const uint32_t* hole_regions, int64_t ox, int64_t oy,
+                                            int64_t oz, int64_t dx, int64_t dy, int64_t dz, int fixed_exponent, float* area,
+                                            uint8_t* contact, uint32_t* voxels, uint8_t* clip, void* scratch, int64_t scratch_bytes,
+                                            void* stream) {
+  const XsHoles hs = {region, hole_begin, hole_count, hole_regions};
+  return xs_launch_box("kh_cross_sections_filled_box", labels, label_bytes, sx, sy, sz, ax, ay, az, n_items, seed_lin, want_label,
+                       normals, &hs, ox, oy, oz, dx, dy, dz, fixed_exponent, area, contact, voxels, clip, scratch, scratch_bytes, stream);
 }
 
 // host: the membership test and the per-voxel area of one voxel at offset (dx, dy, dz) from the seed -- the same inline functions

@@ -278,12 +278,14 @@ class Engine:
                                              self.ptr(d_open), self.ptr(d_out), self.ptr(d_cnt), self.stream()))
         return d_out, int(d_cnt.cpu().numpy()[0])
 
-    def region_graph(self, d_lab, label_bytes, shape, ndim=3, mark=lambda name: None):
+    def region_graph(self, d_lab, label_bytes, shape, ndim=3, mark=lambda name: None, faces=None):
         """The regions of a label volume resident in HBM (6-connected components of equal value, 0 included) and their adjacency:
         kh_regions6 -> kh_region_table -> kh_region_pairs.  Returns (d_region: u32 ids 1..R per voxel on the device; value u64,
         count u32, face u8: host arrays [R + 1]; pairs: host u64, every unordered pair of regions that share a voxel face once, as
         smaller id << 32 | larger id, in no particular order; info: regions, pairs, table_capacity, table_tries, compact_ms).
-        mark(name) is called in front of and behind the launches of each pass (Engine.fill_all_holes puts HIP events there)."""
+        mark(name) is called in front of and behind the launches of each pass (Engine.fill_all_holes puts HIP events there).
+        faces (a box of a dataset, post.region_graph_chunked): the six-bit mask of the faces of the array that are faces of the
+        dataset; `face` then means "owns a voxel on one of those" (kh_region_table_box).  None: every face, kh_region_table."""
         t = self.torch
         sx, sy, sz = shape
         n = sx * sy * sz
@@ -302,8 +304,13 @@ class Engine:
         d_value = self.empty(nreg + 1, t.int64)
         d_count = self.empty(nreg + 1, t.int32)
         d_face = self.empty(nreg + 1, t.uint8)
-        _abi.check(self.lib.kh_region_table(self.ptr(d_lab), int(label_bytes), self.ptr(d_region), self.ptr(d_rep), nreg, int(ndim),
-                                            sx, sy, sz, self.ptr(d_value), self.ptr(d_count), self.ptr(d_face), self.stream()))
+        if faces is None:
+            _abi.check(self.lib.kh_region_table(self.ptr(d_lab), int(label_bytes), self.ptr(d_region), self.ptr(d_rep), nreg, int(ndim),
+                                                sx, sy, sz, self.ptr(d_value), self.ptr(d_count), self.ptr(d_face), self.stream()))
+        else:
+            _abi.check(self.lib.kh_region_table_box(self.ptr(d_lab), int(label_bytes), self.ptr(d_region), self.ptr(d_rep), nreg,
+                                                    int(ndim), sx, sy, sz, int(faces), self.ptr(d_value), self.ptr(d_count),
+                                                    self.ptr(d_face), self.stream()))
         mark("table")
         del d_rep
         # the hash set of region pairs: 32 slots per region to begin with (a region of dense neuropil touches about a dozen others),
@@ -336,6 +343,34 @@ class Engine:
             raise _abi.KimiHipError("kh_region_pairs: %d keys counted, %d found in the table" % (int(state[0]), pairs.size))
         info = dict(regions=nreg, pairs=int(pairs.size), table_capacity=cap, table_tries=tries, compact_ms=(time.perf_counter() - t0) * 1e3)
         return d_region, value, count, face, pairs, info
+
+    def region_seam_pairs(self, d_low, d_high, capacity=None):
+        """kh_region_seam_pairs: the distinct keys low[p] << 32 | high[p] of two facing planes of region ids (u32 on the device, one
+        length m) -> (the keys as a host u64 array in no particular order, the table capacity that held them, the tries).  The
+        table starts at `capacity`, by default the power of two above 4 m slots (at most m keys: a quarter full at the worst), and
+        is tried again 4 x larger when the kernel reports a probe sequence past its limit."""
+        t = self.torch
+        m = int(d_low.numel())
+        assert int(d_high.numel()) == m and m >= 1
+        cap = int(capacity) if capacity else max(1 << max(4 * m - 1, 1).bit_length(), 64)
+        tries = 0
+        while True:
+            tries += 1
+            d_table = self.empty(cap, t.int64)
+            d_state = self.empty(2, t.int32)
+            _abi.check(self.lib.kh_region_seam_pairs(self.ptr(d_low), self.ptr(d_high), m, self.ptr(d_table), cap, self.ptr(d_state),
+                                                     self.stream()))
+            state = d_state.cpu().numpy().view(np.uint32)
+            if state[1] == 0:
+                break
+            if cap >= 64 * m + 4096:
+                raise _abi.KimiHipError("kh_region_seam_pairs: the pair table overflows at %d slots for %d pairs" % (cap, m))
+            del d_table
+            cap *= 4
+        keys = d_table[d_table != 0].cpu().numpy().view(np.uint64)
+        if keys.size != int(state[0]):
+            raise _abi.KimiHipError("kh_region_seam_pairs: %d keys counted, %d found in the table" % (int(state[0]), keys.size))
+        return keys, cap, tries
 
     def fill_all_holes(self, d_lab, label_bytes, shape, ndim=3, stats=None):
         """kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795) on a label volume resident in HBM (1-D, Fortran order, 1 / 2 / 4 /

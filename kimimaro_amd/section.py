@@ -83,8 +83,25 @@ def cross_sections_box(eng, d_lab, label_bytes, box_lo, box_shape, dataset_shape
     return _sections(eng, d_lab, label_bytes, box_shape, anisotropy, seed_lin, want_label, normals, stats, None, (lo, whole))
 
 
+def cross_sections_filled_box(eng, d_lab, label_bytes, box_lo, box_shape, dataset_shape, anisotropy, seed_lin, want_label, normals,
+                              filled, stats=None):
+    """cross_sections_box for the sections of filled(label), hole(label) taken on the DATASET (kh_cross_sections_filled_box; DESIGN.md
+    3.17).  filled = (d_region, hole_begin, hole_count, d_hole_regions) as cross_sections takes it, with d_region the box of the
+    region store on the device (post.region_graph_chunked's provisional ids, u32 per voxel of the box) and the lists in those ids,
+    ascending.  Returns cross_sections_box's four arrays; an item with clip == 0 has what cross_sections(filled=...) gives on the
+    whole dataset, bit for bit in the area."""
+    lo = tuple(int(v) for v in box_lo)
+    whole = tuple(int(v) for v in dataset_shape)
+    if len(lo) != 3 or len(whole) != 3:
+        raise ValueError("box_lo and dataset_shape have three entries")
+    if filled is None:
+        raise ValueError("filled: (d_region, hole_begin, hole_count, d_hole_regions)")
+    return _sections(eng, d_lab, label_bytes, box_shape, anisotropy, seed_lin, want_label, normals, stats, filled, (lo, whole))
+
+
 def _sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, normals, stats, filled, box):
-    """the body of cross_sections (box None: three arrays) and cross_sections_box (box = (box_lo, dataset_shape): four)"""
+    """the body of cross_sections (box None: three arrays) and of cross_sections_box / cross_sections_filled_box (box = (box_lo,
+    dataset_shape): four)"""
     t, P = eng.torch, eng.ptr
     sx, sy, sz = (int(v) for v in shape)
     an = np.asarray(anisotropy, dtype=np.float64).reshape(-1)
@@ -132,8 +149,18 @@ def _sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, 
         stream = t.cuda.current_stream(eng.device)
         before, after = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
         before.record(stream)
+    if filled is not None:
+        d_begin = t.from_numpy(hole_begin.view(np.int32)).to(eng.device)
+        d_count = t.from_numpy(hole_count.view(np.int32)).to(eng.device)
     if box is not None:
         d_clip = eng.empty(n, t.uint8)
+    if box is not None and filled is not None:
+        _abi.check(eng.lib.kh_cross_sections_filled_box(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n,
+                                                        P(d_seed), P(d_want), P(d_normals), P(d_region), P(d_begin), P(d_count),
+                                                        P(d_hole_regions), lo[0], lo[1], lo[2], whole[0], whole[1], whole[2], exponent,
+                                                        P(d_area), P(d_contact), P(d_voxels), P(d_clip), P(d_scratch), nbytes,
+                                                        eng.stream()))
+    elif box is not None:
         _abi.check(eng.lib.kh_cross_sections_box(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n, P(d_seed),
                                                  P(d_want), P(d_normals), lo[0], lo[1], lo[2], whole[0], whole[1], whole[2], exponent,
                                                  P(d_area), P(d_contact), P(d_voxels), P(d_clip), P(d_scratch), nbytes, eng.stream()))
@@ -142,8 +169,6 @@ def _sections(eng, d_lab, label_bytes, shape, anisotropy, seed_lin, want_label, 
                                              P(d_want), P(d_normals), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
                                              eng.stream()))
     else:
-        d_begin = t.from_numpy(hole_begin.view(np.int32)).to(eng.device)
-        d_count = t.from_numpy(hole_count.view(np.int32)).to(eng.device)
         _abi.check(eng.lib.kh_cross_sections_filled(P(d_lab), label_bytes, sx, sy, sz, float(an[0]), float(an[1]), float(an[2]), n,
                                                     P(d_seed), P(d_want), P(d_normals), P(d_region), P(d_begin), P(d_count),
                                                     P(d_hole_regions), P(d_area), P(d_contact), P(d_voxels), P(d_scratch), nbytes,
