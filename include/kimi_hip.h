@@ -496,6 +496,28 @@ int kh_feature_relax(const uint32_t* nbrmask, int64_t sx, int64_t sy, int64_t sz
 int kh_first_appearance(const uint32_t* feature, int64_t nvox, int64_t nnumbers, uint32_t* first_of_number, void* stream);
 int kh_remap_u32(uint32_t* feature, const uint32_t* map, int64_t nnumbers, int64_t nvox, void* stream);
 
+/* ---- the same labels for a dataset that is relaxed box by box (kimimaro_amd.post.oversegment_chunked).  A box is
+ * bx x by x bz voxels (x fastest, < 2^32 in all); its CORE is [core_lo, core_hi) in box-local voxels, half open; core_lo, core_hi
+ * and origin are HOST arrays of three int64.
+ * kh_geodesic_seed_at: kh_geodesic_seed without the init pass -- dist and feature hold what the stores gave; for every seed whose
+ *   voxel carries its label: dist = 0, feature = min(feature, seed_number[s]).  dist or feature may be NULL: that array is left out.
+ * kh_box_shell_diff: one pass over the core that compares the 32-bit words old[v] and now[v] (distances or features).  out: device
+ *   u32 [3], set by the call: [0] bit k = a core voxel changed that lies in the core's outermost layer towards direction k, k in
+ *   kh_neighbor_mask's order (dz, dy, dx from -1 to 1, x fastest, the centre left out) -- a corner voxel sets its corner, its three
+ *   edges and its three faces, and on an axis where the core is one voxel thick a voxel lies in both layers; [1] the core voxels
+ *   that changed; [2] the largest word of now[] over the core below 0x7F800000 (the largest finite non-negative f32 as bits), 0
+ *   when there is none.  Voxels of the box outside the core are not read.
+ * kh_first_appearance_box: first_of_number[n] (u64 [nnumbers + 1]) = min(itself, the smallest DATASET raster index
+ *   (origin + v)_x + SX * ((origin + v)_y + SY * (origin + v)_z) of a core voxel v whose feature is n); features 0 and > nnumbers
+ *   are ignored.  The table is NOT cleared: it accumulates over the boxes of a dataset, the caller sets it to all ones once.       */
+int kh_geodesic_seed_at(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels, int label_bytes,
+                        const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature, void* stream);
+int kh_box_shell_diff(const uint32_t* old, const uint32_t* now, int64_t bx, int64_t by, int64_t bz, const int64_t* core_lo,
+                      const int64_t* core_hi, uint32_t* out, void* stream);
+int kh_first_appearance_box(const uint32_t* feature, int64_t bx, int64_t by, int64_t bz, const int64_t* core_lo,
+                            const int64_t* core_hi, const int64_t* origin, int64_t SX, int64_t SY, int64_t nnumbers,
+                            uint64_t* first_of_number, void* stream);
+
 /* ---- kimimaro.synapses_to_targets (kimimaro/intake.py:706-745): the voxel of a label nearest to a centroid, for all labels and
  * centroids in two passes over the volume (csrc/points.hip).
  * labels: u8/u16/u32/u64 [sx,sy,sz] (label_bytes 1, 2, 4 or 8).  table: u64 [nlabels], the distinct labels asked for as the unsigned

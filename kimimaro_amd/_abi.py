@@ -21,6 +21,7 @@ SYMBOLS = [
     "kh_gather_f32", "kh_init_alive", "kh_level_keys", "kh_invalidate_cube", "kh_invalidate_ball", "kh_path_search", "kh_parental_field", "kh_path_from_parents", "kh_zero2inf", "kh_inf2zero", "kh_pdrf_field", "kh_target_max", "kh_find_target", "kh_first_label", "kh_ccl26", "kh_ccl26_graph", "kh_edt_graph_cells", "kh_edt_graph_sample", "kh_fill_voids", "kh_fill_voids_nd", "kh_host_ccl26", "kh_host_find_border_targets", "kh_host_merge_components",
     "kh_host_consolidate_paths",
     "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
+    "kh_geodesic_seed_at", "kh_box_shell_diff", "kh_first_appearance_box",
     "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
     "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
     "kh_cross_sections_box", "kh_cross_sections_fixed_exponent", "kh_cross_sections_filled_box",
@@ -165,6 +166,9 @@ def lib():
     L.kh_feature_relax.argtypes = [vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, ci, i64, vp]
     L.kh_first_appearance.argtypes = [vp, i64, i64, vp, vp]
     L.kh_remap_u32.argtypes = [vp, vp, i64, i64, vp]
+    L.kh_geodesic_seed_at.argtypes = [vp, vp, i64, vp, ci, vp, i64, vp, vp, vp]
+    L.kh_box_shell_diff.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
+    L.kh_first_appearance_box.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp]
     L.kh_nearest_label_voxels.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp]
     L.kh_binary_edge_count.argtypes = [vp, i64, C.c_uint32, vp, vp, vp, vp]
     L.kh_binary_edge_emit.argtypes = [vp, i64, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]

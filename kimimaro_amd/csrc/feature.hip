@@ -7,6 +7,11 @@
 //   kh_first_appearance  smallest linear index of every number (the renumbering by first appearance in the raster)
 //   kh_remap_u32         feature[v] = map[feature[v]]
 //
+// A dataset that is relaxed box by box (kimimaro_amd.post.oversegment_chunked) runs the same sweeps on a box at a time:
+//   kh_geodesic_seed_at      the seeds alone, on a box whose dist / feature come from the stores
+//   kh_box_shell_diff        which core voxels changed, towards which of the 26 neighbouring cores; the largest finite distance
+//   kh_first_appearance_box  smallest DATASET raster index (64 bits) of every number, accumulated over the boxes
+//
 // Both relaxations are PULL sweeps in place: a thread owns a voxel, reads the neighbour words its mask names and stores with a plain
 // 32-bit store if its value went down.  Values only ever decrease, so a stale read costs a sweep, never a result: the fixpoint is
 // unique and the loop ends when a sweep changed nothing.  Two phases, not one packed (distance, feature) key: see
@@ -41,8 +46,8 @@ __global__ __launch_bounds__(256) void geodesic_seed_kernel(const uint32_t* __re
     if ((int64_t)v >= nvox) continue;                            // (the host drops these already)
     const uint32_t L = seed_label[s];
     if (L == 0 || (uint32_t)lab[v] != L) continue;               // a vertex off its label seeds nothing
-    dist[v] = 0.0f;
-    atomicMin(&feature[v], seed_number[s]);                      // several vertices on one voxel: the smallest number
+    if (dist) dist[v] = 0.0f;
+    if (feature) atomicMin(&feature[v], seed_number[s]);         // several vertices on one voxel: the smallest number
   }
 }
 
@@ -133,6 +138,86 @@ __global__ __launch_bounds__(256) void first_appearance_kernel(const uint32_t* _
   }
 }
 
+// ---- a dataset in boxes.  Both kernels walk the CORE of a box in pieces of 64 voxels of one x row: a wave takes a
+// piece, its lanes lie along x.  piece p: row p / pieces_x (y fastest, then z), voxels 64 * (p % pieces_x) ... of that row.
+struct BoxCore {
+  int32_t bx, by;              // extents of the box (x, y)
+  int32_t lo[3], n[3];         // the core inside the box: its low corner and its extents
+  int32_t pieces_x;            // (n[0] + 63) / 64
+  int64_t pieces;              // pieces_x * n[1] * n[2]
+};
+
+// the box-local coordinates of this lane's voxel of piece p; false: the lane lies past the end of the core row
+__device__ inline bool core_voxel(const BoxCore& c, int64_t p, int lane, int& x, int& y, int& z) {
+  const int64_t row = p / c.pieces_x;
+  const int cx = (int)(p % c.pieces_x) * 64 + lane;
+  x = c.lo[0] + cx;
+  y = c.lo[1] + (int)(row % c.n[1]);
+  z = c.lo[2] + (int)(row / c.n[1]);
+  return cx < c.n[0];
+}
+
+__global__ __launch_bounds__(256) void box_shell_diff_kernel(const uint32_t* __restrict__ old, const uint32_t* __restrict__ now,
+                                                             const BoxCore c, uint32_t* out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * 4;
+  uint32_t dirs = 0, count = 0, top = 0;
+  for (int64_t p = wave; p < c.pieces; p += waves) {
+    int x, y, z;
+    if (!core_voxel(c, p, lane, x, y, z)) continue;
+    const int64_t i = (int64_t)x + (int64_t)c.bx * ((int64_t)y + (int64_t)c.by * z);
+    const uint32_t b = now[i];
+    if (b < 0x7F800000u && b > top) top = b;                 // finite and not negative: the order of the words is the floats'
+    if (old[i] == b) continue;
+    count++;
+    // the outermost layers this voxel lies in (an axis of extent 1: both)
+    const int l[3] = {x == c.lo[0], y == c.lo[1], z == c.lo[2]};
+    const int h[3] = {x == c.lo[0] + c.n[0] - 1, y == c.lo[1] + c.n[1] - 1, z == c.lo[2] + c.n[2] - 1};
+    int k = 0;
+#pragma unroll
+    for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+      for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+          if (dx == 0 && dy == 0 && dz == 0) continue;
+          const int ok = (dx == 0 || (dx < 0 ? l[0] : h[0])) && (dy == 0 || (dy < 0 ? l[1] : h[1])) && (dz == 0 || (dz < 0 ? l[2] : h[2]));
+          dirs |= (uint32_t)ok << k;
+          k++;
+        }
+  }
+  // the wave's result in lane 0, then one atomic of each kind per wave at most
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) {
+    dirs |= __shfl_xor(dirs, s);
+    count += __shfl_xor(count, s);
+    const uint32_t other = __shfl_xor(top, s);
+    top = other > top ? other : top;
+  }
+  if (lane == 0) {
+    if (dirs) atomicOr(&out[0], dirs);
+    if (count) atomicAdd(&out[1], count);
+    if (top) atomicMax(&out[2], top);
+  }
+}
+
+__global__ __launch_bounds__(256) void first_appearance_box_kernel(const uint32_t* __restrict__ feature, const BoxCore c, int64_t ox,
+                                                                   int64_t oy, int64_t oz, int64_t SX, int64_t SY, int64_t nnumbers,
+                                                                   unsigned long long* first_of_number) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), waves = (int64_t)gridDim.x * 4;
+  for (int64_t p = wave; p < c.pieces; p += waves) {            // (p is the same in all lanes of a wave: the shuffle is uniform)
+    int x, y, z;
+    const bool in = core_voxel(c, p, lane, x, y, z);
+    const uint32_t f = in ? feature[(int64_t)x + (int64_t)c.bx * ((int64_t)y + (int64_t)c.by * z)] : 0u;
+    // first_appearance_kernel's trick: the first lane of a run of equal numbers holds the run's smallest index; a piece never leaves
+    // its row, so a run ends where the core row does
+    const uint32_t prev = __shfl_up(f, 1);
+    if ((lane == 0 || f != prev) && f != 0 && (int64_t)f <= nnumbers)
+      atomicMin(&first_of_number[f], (unsigned long long)((ox + x) + SX * ((oy + y) + SY * (oz + z))));
+  }
+}
+
 __global__ __launch_bounds__(256) void remap_u32_kernel(uint32_t* __restrict__ feature, const uint32_t* __restrict__ map, int64_t nnumbers,
                                                         int64_t nvox) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvox; i += (int64_t)gridDim.x * 256) {
@@ -181,21 +266,9 @@ static int relax_impl(bool feature_phase, const uint32_t* nbrmask, int64_t sx, i
   return KH_OK;
 }
 
-}  // namespace kh
-
-using namespace kh;
-
-extern "C" int kh_geodesic_seed(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels,
-                                int label_bytes, const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature,
-                                void* stream) {
-  if (int rc = require_device()) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (nvox <= 0 || nvox >= (int64_t)1 << 32 || nseeds < 0) {
-    set_error("kh_geodesic_seed: 0 < nvox < 2^32 and nseeds >= 0");
-    return KH_EINVAL;
-  }
-  hipLaunchKernelGGL(geodesic_init_kernel, dim3(blocks_for(nvox)), dim3(256), 0, st, dist, feature, nvox);
-  KH_LAUNCH_CHECK();
+// dist / feature: either may be null (kh_geodesic_seed_at)
+static int launch_seeds(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels, int label_bytes,
+                        const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature, hipStream_t st) {
   if (nseeds == 0) return KH_OK;
   switch (label_bytes) {
     case 1:
@@ -214,6 +287,85 @@ extern "C" int kh_geodesic_seed(const uint32_t* seed_voxel, const uint32_t* seed
       set_error("label_bytes must be 1, 2 or 4");
       return KH_EINVAL;
   }
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+// the core [core_lo, core_hi) of a box of bx x by x bz voxels as the kernels take it; false: not inside the box, or the box too large
+static bool make_box_core(BoxCore& c, int64_t bx, int64_t by, int64_t bz, const int64_t* core_lo, const int64_t* core_hi) {
+  const int64_t b[3] = {bx, by, bz};
+  if (bx <= 0 || by <= 0 || bz <= 0 || bx * by * bz >= (int64_t)1 << 32 || !core_lo || !core_hi) return false;
+  for (int a = 0; a < 3; a++) {
+    if (core_lo[a] < 0 || core_lo[a] >= core_hi[a] || core_hi[a] > b[a]) return false;
+    c.lo[a] = (int32_t)core_lo[a];
+    c.n[a] = (int32_t)(core_hi[a] - core_lo[a]);
+  }
+  c.bx = (int32_t)bx;
+  c.by = (int32_t)by;
+  c.pieces_x = (c.n[0] + 63) / 64;
+  c.pieces = (int64_t)c.pieces_x * c.n[1] * c.n[2];
+  return true;
+}
+
+static inline unsigned blocks_for_pieces(int64_t pieces) { return blocks_for(pieces * 64); }      // four waves, four pieces per block
+
+}  // namespace kh
+
+using namespace kh;
+
+extern "C" int kh_geodesic_seed(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels,
+                                int label_bytes, const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature,
+                                void* stream) {
+  if (int rc = require_device()) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (nvox <= 0 || nvox >= (int64_t)1 << 32 || nseeds < 0) {
+    set_error("kh_geodesic_seed: 0 < nvox < 2^32 and nseeds >= 0");
+    return KH_EINVAL;
+  }
+  hipLaunchKernelGGL(geodesic_init_kernel, dim3(blocks_for(nvox)), dim3(256), 0, st, dist, feature, nvox);
+  KH_LAUNCH_CHECK();
+  return launch_seeds(seed_voxel, seed_number, nseeds, labels, label_bytes, seed_label, nvox, dist, feature, st);
+}
+
+extern "C" int kh_geodesic_seed_at(const uint32_t* seed_voxel, const uint32_t* seed_number, int64_t nseeds, const void* labels,
+                                   int label_bytes, const uint32_t* seed_label, int64_t nvox, float* dist, uint32_t* feature,
+                                   void* stream) {
+  if (int rc = require_device()) return rc;
+  if (nvox <= 0 || nvox >= (int64_t)1 << 32 || nseeds < 0) {
+    set_error("kh_geodesic_seed_at: 0 < nvox < 2^32 and nseeds >= 0");
+    return KH_EINVAL;
+  }
+  return launch_seeds(seed_voxel, seed_number, nseeds, labels, label_bytes, seed_label, nvox, dist, feature, (hipStream_t)stream);
+}
+
+extern "C" int kh_box_shell_diff(const uint32_t* old, const uint32_t* now, int64_t bx, int64_t by, int64_t bz, const int64_t* core_lo,
+                                 const int64_t* core_hi, uint32_t* out, void* stream) {
+  if (int rc = require_device()) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  BoxCore c;
+  if (!make_box_core(c, bx, by, bz, core_lo, core_hi)) {
+    set_error("kh_box_shell_diff: a box of 1 .. 2^32 - 1 voxels and 0 <= core_lo < core_hi <= its extents");
+    return KH_EINVAL;
+  }
+  KH_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(uint32_t) * 3, st));
+  hipLaunchKernelGGL(box_shell_diff_kernel, dim3(blocks_for_pieces(c.pieces)), dim3(256), 0, st, old, now, c, out);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_first_appearance_box(const uint32_t* feature, int64_t bx, int64_t by, int64_t bz, const int64_t* core_lo,
+                                       const int64_t* core_hi, const int64_t* origin, int64_t SX, int64_t SY, int64_t nnumbers,
+                                       uint64_t* first_of_number, void* stream) {
+  if (int rc = require_device()) return rc;
+  BoxCore c;
+  if (!make_box_core(c, bx, by, bz, core_lo, core_hi) || !origin || origin[0] < 0 || origin[1] < 0 || origin[2] < 0 ||
+      origin[0] + bx > SX || origin[1] + by > SY || nnumbers < 0 || nnumbers >= 0xFFFFFFFFll) {
+    set_error("kh_first_appearance_box: a box of 1 .. 2^32 - 1 voxels inside the dataset's SX x SY rows, 0 <= core_lo < core_hi <= its "
+              "extents and 0 <= nnumbers < 2^32 - 1");
+    return KH_EINVAL;
+  }
+  hipLaunchKernelGGL(first_appearance_box_kernel, dim3(blocks_for_pieces(c.pieces)), dim3(256), 0, (hipStream_t)stream, feature, c,
+                     origin[0], origin[1], origin[2], SX, SY, nnumbers, (unsigned long long*)first_of_number);
   KH_LAUNCH_CHECK();
   return KH_OK;
 }

@@ -1,7 +1,8 @@
 """Device plumbing of the geodesic Voronoi labels (csrc/feature.hip): seed, relax the distances to their
 fixpoint, relax the features over the achieving edges of the final distances, renumber by first appearance.  Everything works on
 whole-volume arrays resident in HBM; kimimaro_amd.utility.oversegment and kimimaro_amd.ops.euclidean_distance_field(...,
-return_feature_map=True) are the callers."""
+return_feature_map=True) are the callers.  kimimaro_amd.post.oversegment_chunked relaxes a dataset box by box with the same
+kernels; seed_at, relax_box, box_shell_diff, first_appearance_box, first_appearance_map and remap_u32 are its."""
 from __future__ import annotations
 
 import numpy as np
@@ -128,6 +129,87 @@ def geodesic_voronoi(eng, d_lab, label_bytes, shape, anisotropy, seed_voxel, see
         stats.update(distance_sweeps=sweeps_d, feature_sweeps=sweeps_f, distance_bricks=visited_d, feature_bricks=visited_f,
                      bricks=brick_count((sx, sy, sz)), nvox=nvox, nseeds=nseeds)
     return d_dist, (d_feat if features else None)
+
+
+# ---- a dataset in boxes (kimimaro_amd.post.oversegment_chunked) ---------------------------------------------------
+def _i64x3(values):
+    a = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
+    assert a.size == 3
+    return a
+
+
+def _words(eng, a):
+    """u32 host words -> an int32 device tensor (one entry at least: an empty tensor has no pointer)"""
+    t = eng.torch
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    return t.from_numpy(a.view(np.int32)).to(eng.device) if a.size else eng.empty(1, t.int32)
+
+
+def seed_at(eng, d_lab, label_bytes, nvox, seed_voxel, seed_number, seed_label, d_dist=None, d_feat=None):
+    """kh_geodesic_seed_at: the seeds (u32 host arrays as in geodesic_voronoi) into a box whose distances and / or features are
+    there already; an array that is None is left out"""
+    n = int(np.asarray(seed_voxel).size)
+    if n == 0:
+        return
+    P = eng.optr
+    d_sv, d_sn, d_sl = _words(eng, seed_voxel), _words(eng, seed_number), _words(eng, seed_label)
+    _abi.check(eng.lib.kh_geodesic_seed_at(P(d_sv), P(d_sn), n, P(d_lab), label_bytes, P(d_sl), nvox, P(d_dist), P(d_feat), eng.stream()))
+
+
+def relax_box(eng, d_nbr, shape, anisotropy, d_dist, d_feat=None):
+    """the box's distances (d_feat None: kh_geodesic_relax) or its features on these distances (kh_feature_relax) to the box's
+    fixpoint, in place -> sweeps"""
+    P, lib, st = eng.ptr, eng.lib, eng.stream()
+    sx, sy, sz = (int(v) for v in shape)
+    w = [float(v) for v in np.asarray(anisotropy, dtype=np.float32)]
+    if d_feat is None:
+        launch = lambda dirty, changed, n, first: lib.kh_geodesic_relax(P(d_nbr), sx, sy, sz, w[0], w[1], w[2], P(d_dist), P(dirty),
+                                                                        P(changed), n, first, st)
+        return _to_fixpoint(eng, launch, (sx, sy, sz), "kh_geodesic_relax")[0]
+    launch = lambda dirty, changed, n, first: lib.kh_feature_relax(P(d_nbr), sx, sy, sz, w[0], w[1], w[2], P(d_dist), P(d_feat),
+                                                                   P(dirty), P(changed), n, first, st)
+    return _to_fixpoint(eng, launch, (sx, sy, sz), "kh_feature_relax")[0]
+
+
+def box_shell_diff(eng, d_old, d_now, shape, core_lo, core_hi):
+    """kh_box_shell_diff on two device arrays of 32-bit words of a box of `shape` -> (the 26-bit mask of directions, in
+    kh_neighbor_mask's order, towards which a changed core voxel lies in the core's outermost layer; the core voxels that changed;
+    the largest finite non-negative f32 among the core's words of d_now, as bits)"""
+    lo, hi = _i64x3(core_lo), _i64x3(core_hi)
+    d_out = eng.empty(3, eng.torch.int32)
+    _abi.check(eng.lib.kh_box_shell_diff(eng.ptr(d_old), eng.ptr(d_now), int(shape[0]), int(shape[1]), int(shape[2]), _abi.np_ptr(lo),
+                                         _abi.np_ptr(hi), eng.ptr(d_out), eng.stream()))
+    out = d_out.cpu().numpy().view(np.uint32)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def first_appearance_table(eng, total):
+    """the table kh_first_appearance_box accumulates into: int64 [total + 1] on the device, all ones"""
+    return eng.torch.full((int(total) + 1,), -1, dtype=eng.torch.int64, device=eng.device)
+
+
+def first_appearance_box(eng, d_feat, shape, core_lo, core_hi, origin, SX, SY, total, d_first):
+    """kh_first_appearance_box: the smallest dataset raster index of every number 1..total among the core voxels of this box, into
+    d_first (first_appearance_table)"""
+    lo, hi, org = _i64x3(core_lo), _i64x3(core_hi), _i64x3(origin)
+    _abi.check(eng.lib.kh_first_appearance_box(eng.ptr(d_feat), int(shape[0]), int(shape[1]), int(shape[2]), _abi.np_ptr(lo),
+                                               _abi.np_ptr(hi), _abi.np_ptr(org), int(SX), int(SY), int(total), eng.ptr(d_first),
+                                               eng.stream()))
+
+
+def first_appearance_map(first):
+    """first: int64 host array [total + 1], the table of kh_first_appearance_box (-1: the number owns no voxel; entry 0 unused) ->
+    (map u32 [total + 1]: 1..K in the order of the first voxels, 0 for the others; K) -- renumber_first_appearance's map"""
+    first = np.asarray(first, dtype=np.int64)[1:]
+    owned = np.flatnonzero(first >= 0)
+    order = owned[np.argsort(first[owned], kind="stable")]
+    lut = np.zeros(first.size + 1, dtype=np.uint32)
+    lut[order + 1] = np.arange(1, order.size + 1, dtype=np.uint32)
+    return lut, int(order.size)
+
+
+def remap_u32(eng, d_feat, d_map, total, nvox):
+    _abi.check(eng.lib.kh_remap_u32(eng.ptr(d_feat), eng.ptr(d_map), int(total), int(nvox), eng.stream()))
 
 
 def renumber_first_appearance(eng, d_feat, nvox, total, stats=None):

@@ -74,6 +74,15 @@ def _label_of(skel, is_bool):
     return L if L != 0 else None
 
 
+def _oversegment_check_arguments(downsample, fill_holes):
+    """what oversegment and post.oversegment_chunked refuse, before anything else happens"""
+    if downsample > 0:
+        raise NotImplementedError("oversegment(downsample > 0) needs osteoid's Skeleton.downsample, whose source is not available")
+    if fill_holes:
+        raise NotImplementedError("oversegment(fill_holes=True): the reference fills every crop on its own and ADDS overlapping "
+                                  "crops, so a filled hole that holds another label sums two numberings (DESIGN.md 7)")
+
+
 def oversegment(all_labels, skeletons, anisotropy=(1, 1, 1), progress=False, fill_holes=False, in_place=False, downsample=0,
                 _stats=None):
     """kimimaro.oversegment (kimimaro/utility.py:562-644): use skeletons to cut a label volume into one segment per skeleton
@@ -87,12 +96,8 @@ def oversegment(all_labels, skeletons, anisotropy=(1, 1, 1), progress=False, fil
     A skeleton is skipped when its id is 0, its label does not occur or occupies a single voxel (utility.py:141-154); a bool
     volume assigns every skeleton to label 1.  all_labels: numpy, or a torch tensor on the GPU indexed [x, y, z].
     `progress` and `in_place` are accepted and have no effect (nothing is drawn, the input is never written to)."""
-    if downsample > 0:
-        raise NotImplementedError("oversegment(downsample > 0) needs osteoid's Skeleton.downsample, whose source is not available")
-    if fill_holes:
-        raise NotImplementedError("oversegment(fill_holes=True): the reference fills every crop on its own and ADDS overlapping "
-                                  "crops, so a filled hole that holds another label sums two numberings (DESIGN.md 7)")
-    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    _oversegment_check_arguments(downsample, fill_holes)
+    eng = ops.engine()                                  # raises HipUnavailableError without the library or a gfx950 device
     t = eng.torch
     an = np.array(anisotropy, dtype=np.float32).reshape(-1)
     if an.shape != (3,) or not np.all(np.isfinite(an)) or not np.all(an > 0):
