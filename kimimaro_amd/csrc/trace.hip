@@ -15,6 +15,9 @@
 // fixpoint d[v] = min_u fl(d[u] + w), so they equal the oracle's heap Dijkstra bit for bit regardless of
 // the relaxation order; paths are then recovered with the canonical predecessor rule of
 // oracle/kimi_oracle.c (ko_pred / ko_walk), 26 lanes looking at the 26 neighbours at once.
+// Three counters say which parts of a search a call went through -- n_retries (a flush round repeated because an offer found the
+// combine table full), n_spills (a near-list round that began with entries beyond the LDS part) and n_splits (far-list splits);
+// the kernels add them to kh_label_t.stat_search_*, and tests/test_gpu_search_regimes.py asserts them before it compares results.
 //
 // The invalidation flood is order dependent down to the tie order of
 // std::priority_queue, so it is run as an exact emulation of the libstdc++ binary heap in which the 64
@@ -61,6 +64,7 @@ struct Ctl {
   uint32_t u0, u1, u2, u3;
   uint32_t retry[2];     // sssp: a frontier voxel of this batch could not place an offer (parity of the batch)
   uint32_t pool_base;
+  uint32_t n_retries, n_spills, n_splits;   // sssp's regime counters (kh_label_t.stat_search_*): zeroed by the kernel, thread 0 counts
   unsigned long long cyc3[3];
   Geometry g;  // the 26 offsets / edge lengths are indexed per lane: keep them in LDS, not in SGPRs
 };
@@ -357,7 +361,10 @@ __device__ __attribute__((noinline)) void sssp(const Geometry& g_, const uint32_
             }
           }
           const bool again = ctl->retry[par] != 0u;                  // (stable since the barrier above)
-          if (tid == 0) ctl->retry[par ^ 1u] = 0u;                   // (nobody reads or sets the other word before the next barrier)
+          if (tid == 0) {
+            ctl->retry[par ^ 1u] = 0u;                               // (nobody reads or sets the other word before the next barrier)
+            if (again) ctl->n_retries++;
+          }
           par ^= 1u;
           __syncthreads();
           if (!again) break;
@@ -367,6 +374,7 @@ __device__ __attribute__((noinline)) void sssp(const Geometry& g_, const uint32_
         ctl->n_cur = ctl->n_next < q.cap ? ctl->n_next : q.cap;
         ctl->n_next = 0;
         if (ctl->n_far > q.cap) ctl->n_far = q.cap;
+        if (ctl->n_cur > NQ) ctl->n_spills++;                          // the next round reads entries from HBM
       }
       { gu32_t* t = cur; cur = next; next = t; }
       { KH_AS_LDS uint32_t* t = curL; curL = nextL; nextL = t; }
@@ -428,7 +436,11 @@ __device__ __attribute__((noinline)) void sssp(const Geometry& g_, const uint32_
       if (t_far) next[pf] = v;
     }
     __syncthreads();
-    if (tid == 0) { ctl->n_far = ctl->n_far2; ctl->n_far2 = 0; }
+    if (tid == 0) {
+      ctl->n_far = ctl->n_far2; ctl->n_far2 = 0;
+      ctl->n_splits++;
+      if (ctl->n_cur > NQ) ctl->n_spills++;
+    }
     gu32_t* t = far; far = next; next = t;
     __syncthreads();
   }
@@ -515,7 +527,7 @@ __global__ __launch_bounds__(1024) void edf_batch_kernel(kh_label_t* tasks, int 
   const int tid = threadIdx.x;
   if (mode == 1 && task->root != 0xFFFFFFFFu) return;
   const uint32_t source = (mode == 2) ? task->root : task->source;
-  if (tid == 0) { ctl.status = 0; ctl.g = g; }
+  if (tid == 0) { ctl.status = 0; ctl.n_retries = ctl.n_spills = ctl.n_splits = 0; ctl.g = g; }
   __syncthreads();
   Queues q;
   q.cap = task->q_capacity;
@@ -525,7 +537,10 @@ __global__ __launch_bounds__(1024) void edf_batch_kernel(kh_label_t* tasks, int 
   q.touched = q.c + q.cap;
   edf_label(&ctl, task, mode, lists + task->list_offset, task->count, nbrmask, field, qstate, q, delta_floor, source, search_lds,
             KH_SSSP_LDS_BYTES * blockDim.x);
-  if (tid == 0) task->status |= ctl.status;
+  if (tid == 0) {
+    task->status |= ctl.status;
+    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1287,6 +1302,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   uint32_t n_ghost_calls = 0, n_rollbacks = 0;
   if (tid == 0) {
     ctl.status = 0; ctl.u2 = 0; ctl.u3 = 0; ctl.cyc3[0] = ctl.cyc3[1] = ctl.cyc3[2] = 0; ctl.g = g;
+    ctl.n_retries = ctl.n_spills = ctl.n_splits = 0;
     for (int i = 0; i < 5; i++) sweep_stats[i] = 0;
     sweep_setup(sw, &swsh, &ctl, sg, task, nbrmask, alive, q, q.a, nf, heap_top, corner_gate);
   }
@@ -1343,7 +1359,10 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   }
   const uint32_t max_paths = task->max_paths ? task->max_paths : valid;  // trace.py:214-215
   if (nb + na >= max_paths) {                           // trace.py:217-218
-    if (tid == 0) { task->n_paths = 0; task->n_vertices = 0; task->status |= ctl.status; }
+    if (tid == 0) {
+      task->n_paths = 0; task->n_vertices = 0; task->status |= ctl.status;
+      task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+    }
     return;
   }
   if (fix_branching) {
@@ -1564,6 +1583,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
     task->n_paths = npaths;
     task->n_vertices = nverts;
     task->status |= ctl.status;
+    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
     task->stat_settled = ctl.u2;
     task->stat_heap_pushes = ctl.u3;
     task->cyc_target = (uint32_t)(t_target >> 10);
@@ -1656,7 +1676,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void path_search_kernel
   q.b = q.a + q.cap;
   q.c = q.b + q.cap;
   q.touched = q.c + q.cap;
-  if (tid == 0) { ctl.status = 0; ctl.u0 = 0; ctl.g = g; }
+  if (tid == 0) { ctl.status = 0; ctl.u0 = 0; ctl.n_retries = ctl.n_spills = ctl.n_splits = 0; ctl.g = g; }
   __syncthreads();
   if (mode == 1) {
     sssp<2>(ctl.g, nbrmask, pdrf, dist, qstate, src, q, &ctl, 0.0f, search_lds, (uint32_t)sizeof(search_lds));
@@ -1682,7 +1702,10 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void path_search_kernel
     for (uint32_t i = tid; i < nt; i += nthr) { const uint32_t v = q.touched[i]; st_f32_l2(&dist[v], KH_INF); qstate[v] = 0; }
   }
   __syncthreads();
-  if (tid == 0) { *out_n = ctl.u0; task->status |= ctl.status; }
+  if (tid == 0) {
+    *out_n = ctl.u0; task->status |= ctl.status;
+    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

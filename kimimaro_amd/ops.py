@@ -275,6 +275,19 @@ class _Search:
         n = int(d_n.item())
         return coords_of(d_path[:n].cpu().numpy().view(np.uint32), self.shape)
 
+    def parents(self, source):
+        """kh_parental_field from `source` (a linear index): the parents array in the field's shape"""
+        eng, ctx, t, P = self.eng, self.ctx, self.eng.torch, self.eng.ptr
+        sx, sy, sz = self.shape
+        d_par = eng.empty(sx * sy * sz, t.int32)
+        _abi.check(eng.lib.kh_parental_field(P(ctx["d_task"]), P(ctx["d_lists"]), P(ctx["d_nbr"]), sx, sy, sz, P(self.d_field), P(self.d_dist),
+                                             P(ctx["d_qstate"]), P(ctx["d_queues"]), int(source), P(d_par), int(self.graph),
+                                             eng.stream()))
+        status = int(ctx["d_task"].cpu().numpy().view(_abi.LABEL_T)["status"][0])
+        if status:
+            raise _abi.KimiHipError("kh_parental_field: %s" % _abi.describe_status(status))
+        return d_par.cpu().numpy().view(np.uint32).reshape(self.shape, order="F").reshape(self.host_shape, order="F")
+
 
 def railroad(field, source, voxel_graph=None):
     """dijkstra3d.railroad(field, source) as called at kimimaro/trace.py:240-242: the path from `source` to the nearest
@@ -288,16 +301,7 @@ def parental_field(field, source, voxel_graph=None):
     from `source` (uint32, the field's shape, Fortran order; entry = linear index of the predecessor + 1, 0 = none), which the
     caller may edit (`parents[tuple(root)] = 0`, trace.py:220) before handing it to path_from_parents (kh_parental_field)."""
     s = _Search(field, voxel_graph)
-    eng, ctx, t, P = s.eng, s.ctx, s.eng.torch, s.eng.ptr
-    sx, sy, sz = s.shape
-    d_par = eng.empty(sx * sy * sz, t.int32)
-    _abi.check(eng.lib.kh_parental_field(P(ctx["d_task"]), P(ctx["d_lists"]), P(ctx["d_nbr"]), sx, sy, sz, P(s.d_field), P(s.d_dist),
-                                         P(ctx["d_qstate"]), P(ctx["d_queues"]), linear_index(source, s.shape), P(d_par), int(s.graph),
-                                         eng.stream()))
-    status = int(ctx["d_task"].cpu().numpy().view(_abi.LABEL_T)["status"][0])
-    if status:
-        raise _abi.KimiHipError("kh_parental_field: %s" % _abi.describe_status(status))
-    return d_par.cpu().numpy().view(np.uint32).reshape(s.shape, order="F").reshape(s.host_shape, order="F")
+    return s.parents(linear_index(source, s.shape))
 
 
 def path_from_parents(parents, target):

@@ -29,6 +29,10 @@ def test_label_struct_matches_header():
     fields = re.findall(r"\b(?:uint32_t|float)\s+([A-Za-z_0-9, ]+);", body)
     names = [n.strip() for f in fields for n in f.split(",")]
     assert names == list(_abi.LABEL_T.names)
+    # every member is one 32-bit word, and the searches' regime counters were appended: no earlier offset moved
+    assert _abi.LABEL_T.itemsize == 4 * len(names) == 220
+    assert names[-3:] == ["stat_search_retries", "stat_search_spills", "stat_search_splits"]
+    assert _abi.LABEL_T.fields["pdrf_scale"][1] == 204
 
 
 def test_trace_flags_match_header():

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from shapes import random_walk_tube, voronoi_labels
+from voxel_graphs import random_graph as _random_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -724,30 +725,6 @@ def test_function_level_mirrors_match_oracle(eng):
     want = scipy.ndimage.binary_fill_holes(h)
     assert n == int(want.sum()) - int(h.sum()) and n > 0
     np.testing.assert_array_equal(filled.astype(bool), want)
-
-
-def _random_graph(shape, rng, drop, symmetric):
-    """a voxel_graph of cc3d's layout with a fraction of the direction bits cleared; symmetric: an edge is cleared both ways"""
-    class D:   # the 26 directions in the order of dijkstra_invalidation.hpp:60-124 and the bit of each in cc3d's layout (:152-190)
-        DIRS = [(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1), (-1, -1, 0), (-1, 1, 0), (1, -1, 0), (1, 1, 0),
-                (0, -1, -1), (0, -1, 1), (0, 1, -1), (0, 1, 1), (-1, 0, -1), (-1, 0, 1), (1, 0, -1), (1, 0, 1),
-                (-1, -1, -1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1), (1, 1, -1), (1, -1, 1), (-1, 1, 1), (1, 1, 1)]
-        GRAPH_BIT = [1, 0, 3, 2, 5, 4, 9, 7, 8, 6, 17, 13, 16, 12, 15, 11, 14, 10, 25, 24, 23, 21, 22, 20, 19, 18]
-    full = (1 << 26) - 1
-    g = np.full(shape, full, dtype=np.uint32, order="F")
-    for i in range(26):
-        cut = np.asfortranarray(rng.random(shape) < drop)
-        g[cut] &= np.uint32(~(1 << D.GRAPH_BIT[i]) & 0xFFFFFFFF)
-        if symmetric:
-            # the neighbour in direction i loses the opposite bit
-            dx, dy, dz = D.DIRS[i]
-            j = D.DIRS.index((-dx, -dy, -dz))
-            src = np.argwhere(cut)
-            dst = src + np.array([dx, dy, dz])
-            ok = np.all((dst >= 0) & (dst < np.array(shape)), axis=1)
-            dst = dst[ok]
-            g[dst[:, 0], dst[:, 1], dst[:, 2]] &= np.uint32(~(1 << D.GRAPH_BIT[j]) & 0xFFFFFFFF)
-    return g
 
 
 @pytest.mark.parametrize("seed,an,symmetric,fix_branching", [(41, (1, 1, 1), True, True), (42, (16, 16, 40), False, True),
