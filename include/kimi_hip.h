@@ -382,7 +382,10 @@ int kh_ccl26(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_
  * third-party packages whose sources are absent from the reference tree.
  * kh_ccl26_graph replaces cc3d.color_connectivity_graph(voxel_graph, connectivity=26) followed by `cc_labels *= all_labels > 0`:
  * two foreground voxels are joined iff they are 26-neighbours and the graph word (cc3d's bit layout, u32 per voxel) of the later
- * one in the raster allows the step to the earlier one.  Arguments and numbering as kh_ccl26.
+ * one in the raster allows the step to the earlier one.  Arguments and numbering as kh_ccl26.  Also unpinned: it never links two
+ * foreground voxels through background voxels, which color_connectivity_graph(graph) * (labels > 0) can (the mask comes after the
+ * components there).  A component may hold several labels: `representative` is its first voxel, the host names it by the label at
+ * its last run start in the raster (skeletontricks.get_mapping).
  * kh_edt_graph_cells / kh_edt_graph_sample are the two ends of edt.edt(labels, voxel_graph=): cells (u8 [2sx, 2sy, 2sz], F order)
  * receives the doubled image -- voxel (x, y, z) at cell (2x, 2y, 2z); the cell towards +x / +y / +z is foreground iff the voxel is
  * and bit 0 / 2 / 4 of its graph word is set (without black_border: also behind the last voxel of an axis); the other cells of the

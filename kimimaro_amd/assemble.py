@@ -215,11 +215,18 @@ class Assembler:
         code_of_obj = {}
         if keys.size:
             ks = np.argsort(keys, kind="stable")
-            pos = np.searchsorted(keys[ks], np.maximum(seg, 0))
-            pos = np.minimum(pos, keys.size - 1)
+            sorted_keys = keys[ks]
+            pos = np.searchsorted(sorted_keys, np.maximum(seg, 0))
+            found = pos < keys.size
+            found[found] = sorted_keys[pos[found]] == seg[found]
+            pos[~found] = 0
             idx_in_vals = ks[pos]
         else:
+            found = np.zeros(seg.size, dtype=bool)
             idx_in_vals = np.zeros(seg.size, dtype=np.int64)
+        absent = np.flatnonzero((seg >= 0) & ~found)
+        if absent.size:                                         # the reference's remapping[segid] (intake.py:510): no neighbour's label
+            raise KeyError(int(seg[absent[0]]))
         # code per distinct original label VALUE (several component ids map to one label)
         val_code = np.empty(len(vals), dtype=np.int64)
         for i, v in enumerate(vals):

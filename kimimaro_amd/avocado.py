@@ -3,6 +3,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .volume import last_run_starts
+
 
 def _avocado_fruit_from_lines(xl, yl, zl, cx, cy, cz, background=0):
     """kimimaro.skeletontricks.find_avocado_fruit (skeletontricks.pyx:905-992) on the three axis-parallel lines of the label volume
@@ -99,11 +101,8 @@ def engage_avocado_protection_device(eng, d_cc, shape, nlabels, remapping, aniso
     lut = t.zeros(top, dtype=t.int64, device=eng.device)
     lut[by_first] = t.arange(1, by_first.numel() + 1, device=eng.device, dtype=t.int64)
     new = lut[flat]
-    starts = t.ones(nvox, dtype=t.bool, device=eng.device)
-    starts[1:] = new[1:] != new[:-1]
-    sidx = t.nonzero(starts).reshape(-1)
     n_new = int(by_first.numel())
-    last = t.full((n_new + 1,), -1, dtype=t.int64, device=eng.device).scatter_reduce(0, new[sidx], sidx, reduce="amax")
+    last = last_run_starts(t, new, n_new)
     last_h = last.cpu().numpy()
     src = (orig.to(t.int64) & 0xFFFFFFFF)[last.clamp(min=0)].cpu().numpy()
     adjusted = {}

@@ -239,6 +239,11 @@ static int ccl_impl(const LT* lab, int64_t sx, int64_t sy, int64_t sz, uint32_t*
 // joined iff they are 26-neighbours and the graph word of the LATER one in the raster allows the step back to the earlier one
 // (cc3d reads the graph while it rasters; its own graphs are symmetric, so either reading gives the same sets).  Same union-find,
 // numbering and outputs as kh_ccl26.
+// Also unpinned: two foreground voxels are never linked THROUGH background voxels here, while color_connectivity_graph(graph)
+// works on the graph alone and `* (labels > 0)` only masks its result afterwards -- two foreground islands that the graph joins by
+// way of background voxels would share an id there and get two here.
+// A component of the graph may hold several labels; the host names it by the label at its last run start in the raster
+// (skeletontricks.get_mapping, kimimaro/utility.py:82), not by the representative voxel `rep` reports.
 template <typename LT>
 __global__ __launch_bounds__(256) void cclg_init_kernel(const LT* __restrict__ lab, uint32_t* __restrict__ parent, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)

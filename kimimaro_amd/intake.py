@@ -31,7 +31,7 @@ from .avocado import _avocado_fruit_from_lines, engage_avocado_protection_device
 from .holes import enclosed_regions, resolve_holes  # noqa: F401
 from .trace import TRACE_DEFAULTS, point_to_point, trace as trace_one
 from .volume import (DimensionError, LazyVolume, _device_labels, apply_object_mask, coords_of, format_labels,  # noqa: F401
-                     linear_index)
+                     last_run_starts, linear_index)
 
 DEFAULT_TEASAR_PARAMS = {  # kimimaro/intake.py:47-56
     "scale": 1.5,
@@ -68,6 +68,11 @@ def compute_cc_labels(all_labels):
 def compute_cc_labels_device(eng, all_labels, d_graph=None):
     """kimimaro/utility.py:58-83 on the MI355X (kh_ccl26; with a voxel graph kh_ccl26_graph): (device cc volume, N, {cc id: original id})."""
     d_cc, n, rep = eng.ccl(all_labels, d_graph)
+    if d_graph is not None and n:
+        # a graph joins voxels whatever their labels: the voxel get_mapping reads then decides the name -- the component's LAST run
+        # start in the raster.  (Without a graph a component holds one label and its representative voxel says the same.)
+        t = eng.torch
+        rep = last_run_starts(t, d_cc.to(t.int64) & 0xFFFFFFFF, n).cpu().numpy()
     orig = all_labels.reshape(-1, order="F")[rep[1:].astype(np.int64)] if n else []
     remap = {i + 1: orig[i].item() for i in range(n)}  # skeletontricks.get_mapping :490-525
     return d_cc, n, remap
@@ -128,6 +133,10 @@ def skeletonize(all_labels, teasar_params=DEFAULT_TEASAR_PARAMS, anisotropy=(1, 
         avocado = d_dbf_av
     cc = LazyVolume(eng, d_cc, all_labels.shape)
     del d_cc                   # (the volume is reached through `cc` from here on, which lets go of it as soon as it can)
+    # A target belongs to the component that holds its voxel when tracing starts: the points are mapped AFTER the avocado pass.
+    # The reference maps them before it (kimimaro/intake.py:171-172) on ids the pass then merges and renumbers (:187); that order
+    # is NOT reproduced: a target inside a pit is dropped, and one whose old id is reused lands on another label, off its crop
+    # (DESIGN.md section 4).  After fill_holes, as there (:168-172).
     before = _points_to_labels(extra_targets_before, cc)
     after = _points_to_labels(extra_targets_after, cc)
 

@@ -36,6 +36,18 @@ def ranges(starts, counts):
     return np.repeat(np.asarray(starts, dtype=np.int64) - before, counts) + np.arange(total, dtype=np.int64)
 
 
+def last_run_starts(t, ids, n):
+    """skeletontricks.get_mapping's choice of voxel (skeletontricks.pyx:490-525) on the device: the raster (x fastest) is walked
+    once and an id is (re)named wherever it differs from the PREVIOUS voxel's -- the last such place wins.  ids: int64 device tensor
+    of the flat component volume, values 0..n.  Returns an int64 device tensor [n + 1]: per id the linear index of its last run
+    start, -1 for an id that does not occur."""
+    nvox = ids.numel()
+    starts = t.ones(nvox, dtype=t.bool, device=ids.device)
+    starts[1:] = ids[1:] != ids[:-1]
+    sidx = t.nonzero(starts).reshape(-1)
+    return t.full((n + 1,), -1, dtype=t.int64, device=ids.device).scatter_reduce(0, ids[sidx], sidx, reduce="amax")
+
+
 def format_labels(labels, in_place=False):
     """The input as a Fortran-ordered array with exactly three axes, as kimimaro/intake.py:315-342 prepares it: bool
     volumes are reinterpreted as uint8, 1-D / 2-D inputs get trailing axes of extent 1, trailing singleton axes

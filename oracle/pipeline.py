@@ -231,15 +231,10 @@ def format_labels(labels):
 
 
 def compute_cc_labels(all_labels, voxel_graph=None):
-    """kimimaro/utility.py:58-83: returns (cc_labels, {cc id: original id})."""
+    """kimimaro/utility.py:58-83: returns (cc_labels, {cc id: original id}).  The ids are named by get_mapping (:81): with a
+    voxel graph a component can hold several labels, and the one at its last run start in the raster names it."""
     cc, n = K.connected_components(all_labels) if voxel_graph is None else K.color_connectivity_graph(all_labels, voxel_graph)
-    first = np.zeros(n + 1, dtype=np.int64)
-    flat_cc = cc.ravel(order="F")
-    idx = np.flatnonzero(flat_cc)
-    # first occurrence of each component -> original label there
-    uniq, first_idx = np.unique(flat_cc[idx], return_index=True)
-    orig = all_labels.ravel(order="F")[idx[first_idx]]
-    remap = {int(u): orig[i].item() for i, u in enumerate(uniq)}
+    remap = {k: v for k, v in get_mapping(all_labels, cc).items() if k != 0}
     return cc, remap
 
 
@@ -351,8 +346,12 @@ def get_mapping(orig_labels, cc_labels):
     if o.size == 0:
         return remap
     starts = np.flatnonzero(np.concatenate([[True], c[1:] != c[:-1]]))
-    for i in starts:            # ascending: later run starts overwrite earlier ones
-        remap[int(c[i])] = o[i].item()
+    # ascending: later run starts overwrite earlier ones, a key keeps the place of its first run
+    ids, first = np.unique(c[starts], return_index=True)
+    _, from_end = np.unique(c[starts][::-1], return_index=True)
+    last = starts[starts.size - 1 - from_end]
+    for k in np.argsort(first, kind="stable"):
+        remap[int(ids[k])] = o[last[k]].item()
     return remap
 
 
@@ -412,9 +411,6 @@ def skeletonize(all_labels, teasar_params=DEFAULT_TEASAR_PARAMS, anisotropy=(1, 
     if fill_holes:
         cc_labels = fill_all_holes(cc_labels)                                    # intake.py:168-169
 
-    before = _points_to_labels(extra_targets_before, cc_labels)
-    after = _points_to_labels(extra_targets_after, cc_labels)
-
     if voxel_graph is not None:
         all_dbf = K.edt_graph(cc_labels, voxel_graph, anisotropy, black_border=(minlabel == maxlabel))
     else:
@@ -423,6 +419,13 @@ def skeletonize(all_labels, teasar_params=DEFAULT_TEASAR_PARAMS, anisotropy=(1, 
         cc_labels, all_dbf, remapping = engage_avocado_protection(
             cc_labels, all_dbf, remapping, teasar_params.get("soma_detection_threshold", 0),
             lambda lab: K.edt(lab, anisotropy, black_border=(minlabel == maxlabel)))
+
+    # A target belongs to the component that holds its voxel when tracing starts: the points are mapped AFTER the avocado pass, as
+    # the product does.  The reference maps them before it (kimimaro/intake.py:171-172) on ids the pass then merges and renumbers
+    # (:187); that order is NOT reproduced: a target inside a pit is dropped, and one whose old id is reused lands on another
+    # label, off its crop.  After fill_holes, as there (:168-172).
+    before = _points_to_labels(extra_targets_before, cc_labels)
+    after = _points_to_labels(extra_targets_after, cc_labels)
 
     counts = np.bincount(cc_labels.ravel(order="F"))
     cc_segids = [i for i in range(1, counts.size) if counts[i] > dust_threshold]

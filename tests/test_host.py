@@ -108,6 +108,75 @@ def test_assembler_merge_equals_simple_merge_consolidate():
         assert got[orig].id == orig and got[orig].space == "physical"
 
 
+def _assembler_groups(remapping, seed=7):
+    """Assembler fed the way Engine.run_labels feeds it (`add` of a result group): three groups, the components of `remapping`
+    out of order over them, one slot without vertices, one component whose only path has a single vertex (no edge: dropped).
+    Returns (assembler, {component id: (verts, edges, radii) as consolidate_paths gives them})."""
+    from kimimaro_amd.intake import Assembler, consolidate_paths
+    rng = np.random.default_rng(seed)
+    shape = (40, 30, 20)
+    asm = Assembler(shape, (16.0, 16.0, 40.0), remapping)
+    pool, at = rng.permutation(int(np.prod(shape))), 0
+    parts = {}
+    for segids in ([1000, 3, 77777], [17], [40, 88888]):              # 77777: an empty slot, 88888: one vertex (ids not in the dict)
+        verts, radii, lens, voff, loff = [], [], [], [0], [0]
+        for comp in segids:
+            if comp == 77777:
+                paths = []
+            elif comp == 88888:
+                paths = [pool[at:at + 1]]
+                at += 1
+            else:
+                a, b = pool[at:at + 20], pool[at + 20:at + 31]
+                at += 31
+                paths = [a, np.concatenate([a[7:8], b])]             # the second path starts on the first (shared vertex)
+            r = [rng.random(p.size).astype(np.float32) for p in paths]
+            if len(paths) == 2:
+                r[1][0] = r[0][7]
+                parts[comp] = consolidate_paths(np.concatenate(paths).astype(np.int64), np.array([20, 12], dtype=np.int64),
+                                                np.concatenate(r), shape)
+            verts.extend(paths)
+            radii.extend(r)
+            lens.extend(p.size for p in paths)
+            voff.append(voff[-1] + sum(p.size for p in paths))
+            loff.append(loff[-1] + len(paths))
+        asm.add({"verts": np.concatenate(verts).astype(np.uint32), "radii": np.concatenate(radii), "lens": np.asarray(lens, dtype=np.uint32),
+                 "voff": np.asarray(voff), "loff": np.asarray(loff), "tasks": {"segid": np.asarray(segids, dtype=np.uint32)}})
+    return asm, parts
+
+
+def test_assembler_groups_look_up_sparse_component_ids():
+    """Assembler.finish through `groups`, the route Engine.run_labels takes: the component ids are sparse and not in dict order,
+    a label has several components and they arrive out of order; every label equals Skeleton.simple_merge(components).consolidate()
+    (kimimaro/intake.py:587-593).  A component whose id is missing from the remapping is a KeyError naming it, as `remapping[segid]`
+    is in the reference (intake.py:510) -- never a skeleton under a neighbouring key's label."""
+    from kimimaro_amd.skeleton import Skeleton
+    remapping = {40: 7, 3: 9, 17: 7, 1000: 5}
+    an = np.float32([16.0, 16.0, 40.0])
+    asm, parts = _assembler_groups(remapping)
+    assert len(asm.groups) == 3 and not asm.skeletons and sorted(parts) == sorted(remapping)
+    got = asm.finish()
+    assert list(got) == [5, 9, 7]                                     # labels by first arrival
+    for orig in (5, 9, 7):
+        sk = [Skeleton(np.multiply(parts[c][0], an, dtype=np.float32), parts[c][1], radii=parts[c][2], segid=orig)
+              for c in sorted(remapping) if remapping[c] == orig]
+        assert len(sk) == (2 if orig == 7 else 1)
+        want = Skeleton.simple_merge(sk).consolidate()
+        np.testing.assert_array_equal(got[orig].vertices, want.vertices)
+        np.testing.assert_array_equal(got[orig].edges, want.edges)
+        np.testing.assert_array_equal(got[orig].radii, want.radii)
+        assert got[orig].id == orig and got[orig].space == "physical"
+    for missing in (3, 17, 40, 1000):                                 # below all keys, between two keys (twice), above all keys
+        less = {k: v for k, v in remapping.items() if k != missing}
+        asm, _ = _assembler_groups(less)
+        with pytest.raises(KeyError) as err:
+            asm.finish()
+        assert err.value.args == (missing,)
+    asm, _ = _assembler_groups({})
+    with pytest.raises(KeyError):
+        asm.finish()
+
+
 def test_oracle_pool_equals_serial_oracle():
     """oracle/pool.py (per-component work on a forked pool, DBF on the component's box grown by one voxel and cut back
     to the reference's crop) gives exactly oracle.pipeline.skeletonize's result."""

@@ -170,3 +170,39 @@ def test_fix_avocados_merges_pits_into_their_fruit():
     assert set(fixed) == {11, 21, 31, 41, 51}            # ... and gone with it
     for k in (41, 51):
         np.testing.assert_array_equal(fixed[k].vertices, plain[k].vertices)
+
+
+@pytest.mark.parametrize("fix_borders", [False, True])
+@pytest.mark.parametrize("side", ["extra_targets_before", "extra_targets_after"])
+def test_avocado_targets_belong_to_the_component_tracing_starts_with(side, fix_borders):
+    """the project's rule, NOT the reference's order (kimimaro/intake.py:171-172 before :187): the extra
+    targets are mapped on the components the avocado pass left, so a target inside a pit is a vertex of the pit's fruit"""
+    import bookkeeping_cases as B
+    from shapes import avocado_volume
+    an = B.AVOCADO_AN
+    kw = dict(teasar_params=B.avocado_params(P.DEFAULT_TEASAR_PARAMS), anisotropy=an, dust_threshold=50, fix_borders=fix_borders,
+              fix_avocados=True)
+    lab = avocado_volume()
+    plain = P.skeletonize(lab, **kw)
+    assert B.holders(plain, (47, 58, 40), an) == []
+    got = P.skeletonize(lab, **kw, **{side: list(B.AVOCADO_TARGETS)})
+    assert sorted(got) == [11, 21, 31, 41, 51]
+    for pt, key in B.AVOCADO_TARGETS.items():
+        assert B.holders(got, pt, an) == [key], (pt, key)
+
+
+@pytest.mark.parametrize("an,fix_borders", [((1, 1, 1), True), ((16, 16, 40), False)])
+def test_graph_component_is_named_by_its_last_run_start(an, fix_borders):
+    """kimimaro/utility.py:82 + skeletontricks.pyx:490-525: one graph component of labels 7 and 9 whose first and last voxels say 7
+    and whose last run start says 9 is skeleton 9; with a wall across it, two components, one id each"""
+    import bookkeeping_cases as B
+    kw = dict(teasar_params=B.graph_params(an), anisotropy=an, dust_threshold=20, fix_borders=fix_borders)
+    lab, g = B.spanning_block(wall=False)
+    assert P.compute_cc_labels(lab, g)[1] == {1: 9}
+    got = P.skeletonize(lab, voxel_graph=g, **kw)
+    assert list(got) == [9] and got[9].id == 9 and got[9].vertices.shape[0] >= 10
+    lab, g = B.spanning_block(wall=True)
+    assert P.compute_cc_labels(lab, g)[1] == {1: 9, 2: 7}
+    got = P.skeletonize(lab, voxel_graph=g, **kw)
+    assert sorted(got) == [7, 9]
+    assert got[9].vertices[:, 0].max() <= 11 * an[0] < 12 * an[0] <= got[7].vertices[:, 0].min()
