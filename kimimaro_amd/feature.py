@@ -1,7 +1,7 @@
 """Device plumbing of the geodesic Voronoi labels (csrc/feature.hip): seed, relax the distances to their
 fixpoint, relax the features over the achieving edges of the final distances, renumber by first appearance.  Everything works on
 whole-volume arrays resident in HBM; kimimaro_amd.utility.oversegment and kimimaro_amd.ops.euclidean_distance_field(...,
-return_feature_map=True) are the callers.  kimimaro_amd.post.oversegment_chunked relaxes a dataset box by box with the same
+return_feature_map=True) are the callers.  kimimaro_amd.segment_boxes.oversegment_chunked relaxes a dataset box by box with the same
 kernels; seed_at, relax_box, box_shell_diff, first_appearance_box, first_appearance_map and remap_u32 are its."""
 from __future__ import annotations
 
@@ -131,7 +131,7 @@ def geodesic_voronoi(eng, d_lab, label_bytes, shape, anisotropy, seed_voxel, see
     return d_dist, (d_feat if features else None)
 
 
-# ---- a dataset in boxes (kimimaro_amd.post.oversegment_chunked) ---------------------------------------------------
+# ---- a dataset in boxes (kimimaro_amd.segment_boxes.oversegment_chunked) ---------------------------------------------------
 def _i64x3(values):
     a = np.ascontiguousarray(values, dtype=np.int64).reshape(-1)
     assert a.size == 3

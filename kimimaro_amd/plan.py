@@ -403,7 +403,23 @@ def core_of(vox, shape, chunk_shape):
     vox = np.asarray(vox, dtype=np.int64).reshape(-1, 3)
     extent = np.array((tuple(int(v) for v in shape) + (1,))[:3], dtype=np.int64)
     chunk = np.array((tuple(int(v) for v in chunk_shape) + (1,))[:3], dtype=np.int64)
-    grid = (extent + chunk - 1) // chunk
-    k = vox // chunk
     inside = np.all((vox >= 0) & (vox < extent), axis=1)
-    return np.where(inside, k[:, 0] + grid[0] * (k[:, 1] + grid[1] * k[:, 2]), -1)
+    return np.where(inside, _raster((extent + chunk - 1) // chunk, vox // chunk), -1)
+
+
+def _raster(grid, at):
+    """the row, x fastest, of the chunk at grid position `at` (int64 [..., 3]) in a grid of `grid` chunks per axis"""
+    return at[..., 0] + int(grid[0]) * (at[..., 1] + int(grid[1]) * at[..., 2])
+
+
+def core_index(grid, at):
+    """grid positions `at` (int [..., 3]) in a grid of `grid` chunks per axis (ChunkGrid.grid) -> int64 [...]: the row of that chunk
+    -- the inverse of ChunkGrid.grid_index --, -1 for a position outside the grid"""
+    at = np.asarray(at, dtype=np.int64)
+    return np.where(np.all((at >= 0) & (at < np.asarray(grid, dtype=np.int64)), axis=-1), _raster(grid, at), -1)
+
+
+def neighbor_cores(grid, steps):
+    """int64 [chunks, len(steps)]: per chunk of the ChunkGrid `grid` the row of the chunk one step (dx, dy, dz) away in the grid, for each
+    of `steps`; -1 where the grid ends"""
+    return core_index(grid.grid, grid.grid_index[:, None, :] + np.asarray(steps, dtype=np.int64).reshape(1, -1, 3))

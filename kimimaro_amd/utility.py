@@ -75,7 +75,7 @@ def _label_of(skel, is_bool):
 
 
 def _oversegment_check_arguments(downsample, fill_holes):
-    """what oversegment and post.oversegment_chunked refuse, before anything else happens"""
+    """what oversegment and segment_boxes.oversegment_chunked refuse, before anything else happens"""
     if downsample > 0:
         raise NotImplementedError("oversegment(downsample > 0) needs osteoid's Skeleton.downsample, whose source is not available")
     if fill_holes:

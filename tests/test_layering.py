@@ -1,5 +1,5 @@
 """The host package is layered: module-level imports inside kimimaro_amd only go downward in ORDER, nothing but Engine.soma_lane_pool
-imports a sibling inside a function, and what left intake.py for a module of its own is still reachable there.  No GPU, no library:
+imports a sibling inside a function, and what left intake.py or post.py for a module of its own is still reachable there.  No GPU, no library:
 the import graph is read from the source with ast."""
 import ast
 import importlib
@@ -11,7 +11,7 @@ PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 
 # low to high: a module imports, at module level, only modules in front of it
 ORDER = ("_abi", "skeleton", "build", "plan", "volume", "holes", "border", "assemble", "engine", "feature", "points", "section",
-         "ops", "trace", "avocado", "intake", "utility", "lanes", "distributed", "post")
+         "ops", "trace", "avocado", "intake", "utility", "lanes", "distributed", "boxes", "section_boxes", "segment_boxes", "post")
 
 # name -> the module that defines it; each is the same object as kimimaro_amd.intake.NAME
 LEGACY = {
@@ -24,6 +24,13 @@ LEGACY = {
     "skeletonize": "intake", "skeletonize_cc": "intake", "shard_components": "intake", "compute_cc_labels": "intake",
     "compute_cc_labels_device": "intake", "fill_all_holes": "intake", "fill_all_holes_device": "intake",
     "synapses_to_targets": "intake", "connect_points": "intake", "DEFAULT_TEASAR_PARAMS": "intake",
+}
+
+# name -> the module that defines it; each is the same object as kimimaro_amd.post.NAME
+POST = {
+    "region_graph_chunked": "section_boxes", "hole_lists": "section_boxes", "RegionGraph": "section_boxes",
+    "cross_sectional_area_chunked": "section_boxes", "cross_sectional_area_filled_chunked": "section_boxes", "XS_CLIPPED": "section_boxes",
+    "oversegment_chunked": "segment_boxes", "shell_diff": "segment_boxes", "DIRECTIONS": "segment_boxes",
 }
 
 
@@ -80,4 +87,13 @@ def test_legacy_name_is_the_same_object(name):
     home = importlib.import_module("kimimaro_amd." + LEGACY[name])
     assert hasattr(intake, name), "kimimaro_amd.intake.%s is gone" % name
     assert getattr(intake, name) is getattr(home, name)
+    assert getattr(getattr(home, name), "__module__", home.__name__) == home.__name__     # defined there, not passed through
+
+
+@pytest.mark.parametrize("name", sorted(POST))
+def test_post_name_is_the_same_object(name):
+    post = importlib.import_module("kimimaro_amd.post")
+    home = importlib.import_module("kimimaro_amd." + POST[name])
+    assert hasattr(post, name), "kimimaro_amd.post.%s is gone" % name
+    assert getattr(post, name) is getattr(home, name)
     assert getattr(getattr(home, name), "__module__", home.__name__) == home.__name__     # defined there, not passed through
