@@ -1,4 +1,4 @@
-/* systolic_heap_sim.c -- CPU model of the lock-step pipelined heap of csrc/trace.hip (round 3), lane for lane.
+/* systolic_heap_sim.c -- CPU model of the lock-step pipelined heap that csrc/trace.hip had in round 3 (the heap is csrc/heap.h now), lane for lane.
  *
  * TEST / DESIGN INFRASTRUCTURE (never part of the product).  Three executions of the same flood
  * (dijkstra_invalidation.hpp:239-332) on a random blob, which must agree in the sequence of pops (key, voxel, source,

@@ -154,7 +154,7 @@ typedef struct kh_label_t {
   /* KH_TRACE_FUSED_EDF: compute_pdrf's parameters (kimimaro/trace.py:315-356, the repeated-squaring branch) */
   uint32_t pdrf_log2e;   /* in: log2 of pdrf_exponent */
   float pdrf_scale;      /* in: pdrf_scale */
-  /* regime counters of the searches (csrc/trace.hip sssp; kh_edf_batch, kh_path_search and kh_trace_paths ADD to them): what
+  /* regime counters of the searches (csrc/sssp.h sssp; kh_edf_batch, kh_path_search and kh_trace_paths ADD to them): what
      tests/test_gpu_search_regimes.py asserts before it compares a result */
   uint32_t stat_search_retries; /* out: flush rounds repeated because an offer found the combine table full */
   uint32_t stat_search_spills;  /* out: near-list rounds that started with more entries than the LDS part holds */

@@ -4,6 +4,7 @@ In-tree build (the .so travels to the GPU box with the snapshot; it is git-ignor
 -ffp-contract=off: no FMA contraction anywhere -- squared distances, PDRF and Dijkstra sums must be
 rounded op by op exactly like numpy / the reference's g++ build / the oracle.
 """
+import glob
 import os
 import subprocess
 
@@ -11,7 +12,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkimi_hip.so")
 SOURCES = ["common.hip", "edt.hip", "prep.hip", "trace.hip", "ccl.hip", "feature.hip", "points.hip", "section.hip", "join.hip"]
-DEPS = SOURCES + ["common.h", "sweep.h", os.path.join("..", "..", "include", "kimi_hip.h")]
+# what a change of asks for a rebuild (paths from CSRC): the sources, EVERY header next to them, the C ABI
+DEPS = (SOURCES + sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h")))
+        + [os.path.join("..", "..", "include", "kimi_hip.h")])
 
 
 def needs_build():

@@ -38,6 +38,9 @@ static constexpr float KH_INF = __builtin_huge_valf();
 // it -- a field of an LDS-resident record, an entry of the geometry table -- waits for it to RETURN (s_waitcnt vmcnt(0)
 // lgkmcnt(0)), which turns loads that could travel together into a chain of round trips.  With the address space in the type the
 // ISA shows global_load / global_atomic / ds_* and only real dependences wait.
+// Inside the searches (sssp.h) the same holds for the pointers that arrive through a function boundary as generic ones: an LDS
+// read between two flat accesses would wait for the first to return; typed, the loads are global_load / ds_read and the search's
+// stages really overlap.
 #define KH_AS_GLOBAL __attribute__((address_space(1)))
 #define KH_AS_LDS __attribute__((address_space(3)))
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));   // (HIP's uint2 / uint4 are structs: no copies across address spaces)

@@ -37,6 +37,7 @@
 // integer/f32 work bound by dependent round trips to L2 / HBM (about ten per level).
 #pragma once
 #include "common.h"
+#include "rows27.h"
 
 namespace kh {
 
@@ -377,9 +378,7 @@ __device__ __forceinline__ uint32_t sweep_mask(SweepRef s, uint32_t v, uint32_t 
 // (global_load_dwordx3; plain loads: the words are only ever written by plain stores of this workgroup, i.e. through this CU's own
 // vector cache -- a first version read them with the nt hint, which keeps them out of the L2 as well: 512 GB per volume against
 // 447 in round 5, hit rate 0.56), their addresses depend on nothing but v, so they travel with the event's own words; and in
-// integer mode the levels are arithmetic.
-typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
-typedef u32x3_t u32x3_a4_t __attribute__((aligned(4)));
+// integer mode the levels are arithmetic.  (u32x3_t / u32x3_a4_t: rows27.h)
 // w[(dx + 1) + 3 * ((dy + 1) + 3 * (dz + 1))] = filter word of the voxel at (x + dx, y + dy, z + dz); rows outside the volume
 // read v's own row (their neighbours are not in anybody's mask)
 __device__ __forceinline__ void sweep_rows(const KH_AS_GLOBAL uint32_t* sched, int sx, int sxy, int sy, int sz, uint32_t v, int y, int z,

@@ -1,5 +1,7 @@
-// trace.hip -- the per-label TEASAR searches for gfx950: one workgroup per label (512 threads for the
-// distance fields, one 64-lane wave for the path loop).
+// trace.hip -- the kernels and entry points of the per-label TEASAR searches for gfx950: one workgroup per label (512 threads by
+// default for the distance fields, 256 -- or 128 / 64 by flag -- for the path loop).  ONE translation unit: the machines the
+// kernels are made of live in headers of their own and are compiled here, together (the sweep's out-of-line functions inherit
+// the register bound of the kernels that reach them, see invalidate_ball_kernel).
 //
 //   kh_edf_batch    a4  dijkstra3d.euclidean_distance_field   (kimimaro/trace.py:139-145, 302-307)
 //   kh_trace_paths  a6-a11 compute_paths loop                 (kimimaro/trace.py:196-267):
@@ -7,516 +9,42 @@
 //                     railroad        dijkstra3d.railroad, trace.py:240-242
 //                     invalidation    skeletontricks.pyx:373-418 -> dijkstra_invalidation.hpp:239-332
 //                     rail edits      trace.py:220, 261-263
+//   kh_invalidate_ball, kh_path_search, kh_parental_field, kh_path_from_parents, kh_invalidate_cube, kh_level_keys
+//                   a7-a10 one at a time, on the same device routines
 //
-// Search = label-correcting relaxation with a near/far split (delta-stepping with an adaptive
-// threshold): work items are (frontier voxel, direction) pairs spread over the lanes, distances are
-// float bit patterns updated with atomicMin, the work lists hold voxel indices only (membership bits in
-// `qstate` keep every list bounded by the label size).  The distances converge to the unique Bellman
-// fixpoint d[v] = min_u fl(d[u] + w), so they equal the oracle's heap Dijkstra bit for bit regardless of
-// the relaxation order; paths are then recovered with the canonical predecessor rule of
-// oracle/kimi_oracle.c (ko_pred / ko_walk), 26 lanes looking at the 26 neighbours at once.
-// Three counters say which parts of a search a call went through -- n_retries (a flush round repeated because an offer found the
-// combine table full), n_spills (a near-list round that began with entries beyond the LDS part) and n_splits (far-list splits);
-// the kernels add them to kh_label_t.stat_search_*, and tests/test_gpu_search_regimes.py asserts them before it compares results.
+//   search_state.h  Ctl, Queues, the membership flags and the L2 loads / stores every machine shares
+//   rows27.h        the 27 words around a voxel as nine rows of three (searches and sweep)
+//   sssp.h          Search = label-correcting relaxation with a near/far split (delta-stepping with an adaptive threshold): one
+//                   thread per frontier voxel, distances are float bit patterns, the offers of a batch are combined by an LDS
+//                   atomic min and written by one thread each, the work lists hold voxel indices only (membership bits in `qstate`
+//                   keep every list bounded by the label size).  The distances converge to the unique Bellman fixpoint
+//                   d[v] = min_u fl(d[u] + w), so they equal the oracle's heap Dijkstra bit for bit regardless of the relaxation
+//                   order.  Three counters say which parts of a search a call went through -- n_retries (a flush round repeated
+//                   because an offer found the combine table full), n_spills (a near-list round that began with entries beyond the
+//                   LDS part) and n_splits (far-list splits); the kernels add them to kh_label_t.stat_search_*, and
+//                   tests/test_gpu_search_regimes.py asserts them before it compares results.
+//   backtrack.h     paths are recovered with the canonical predecessor rule of oracle/kimi_oracle.c (ko_pred / ko_walk), 26 lanes
+//                   looking at the 26 neighbours at once.
+//   heap.h          The invalidation flood is order dependent down to the tie order of std::priority_queue, so it
+//                   is run as an exact emulation of the libstdc++ binary heap in which the 64 lanes of the label's first wave
+//                   cooperate on every push and pop, with the 26 neighbour tests of each popped voxel evaluated by 26 lanes.
+//   sweep.h         the order-free evaluation of the same flood, which certifies most calls without the heap
+//   invalidate.h    one invalidation call: sweep first, heap emulation as the fall-back; scratch pool, ghosts
 //
-// The invalidation flood is order dependent down to the tie order of
-// std::priority_queue, so it is run as an exact emulation of the libstdc++ binary heap in which the 64
-// lanes of the label's wave cooperate on every push and pop (see "The invalidation heap" below), with
-// the 26 neighbour tests of each popped voxel evaluated by 26 lanes.
-//
-// No MFMA: irregular, latency/atomic bound integer+f32 work (north_star).  Labels are independent, so
-// the chip is filled by running every label's workgroup concurrently; the largest labels keep two
-// chunks of their heap in LDS (kh_trace_paths n_large).
+// No MFMA: irregular, latency/atomic bound integer+f32 work (north_star).  Labels are independent, so the chip is filled by running
+// every label's workgroup concurrently; KH_TRACE_BIG_LDS_HEAP keeps two chunks of every label's heap in LDS (Heap<2>).
 #include <stdlib.h>
 
 #include "common.h"
 #include "sweep.h"
+#include "search_state.h"
+#include "rows27.h"
+#include "sssp.h"
+#include "heap.h"
+#include "backtrack.h"
+#include "invalidate.h"
 
 namespace kh {
-
-static constexpr uint32_t INF_BITS = 0x7f800000u;
-static constexpr unsigned long long NONE64 = ~0ull;
-
-__device__ __forceinline__ float ld_f32_l2(const float* p) {
-  // dist words are modified by L2 atomics; read them at agent scope (bypasses the per-CU L1)
-  return __uint_as_float(__hip_atomic_load(reinterpret_cast<const uint32_t*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void st_f32_l2(float* p, float v) {
-  __hip_atomic_store(reinterpret_cast<uint32_t*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned long long pack(float d, uint32_t v) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | v;
-}
-__device__ __forceinline__ float next_up(float x) { return __uint_as_float(__float_as_uint(x) + 1u); }
-// read lane `l` (wave-uniform index) of a 32-bit value: v_readlane instead of a ds_bpermute round trip
-__device__ __forceinline__ uint32_t rdlane_u32(uint32_t v, int l) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, __builtin_amdgcn_readfirstlane(l));
-}
-struct Ctl {
-  unsigned long long best_rail;
-  unsigned long long red64[16];
-  uint32_t n_cur, n_next, n_far, n_far2, n_touched;
-  uint32_t status;
-  float red_min[16];
-  float red_sum[16];
-  uint32_t red_cnt[16];
-  float T;
-  uint32_t u0, u1, u2, u3;
-  uint32_t retry[2];     // sssp: a frontier voxel of this batch could not place an offer (parity of the batch)
-  uint32_t pool_base;
-  uint32_t n_retries, n_spills, n_splits;   // sssp's regime counters (kh_label_t.stat_search_*): zeroed by the kernel, thread 0 counts
-  unsigned long long cyc3[3];
-  Geometry g;  // the 26 offsets / edge lengths are indexed per lane: keep them in LDS, not in SGPRs
-};
-
-// work lists hold voxel indices only; membership is tracked by two bits per voxel in `qstate`
-// (bit0: queued in the near list being built, bit1: queued in the far list), so a voxel is in each
-// list at most once and every list is bounded by the label size Nf.
-struct Queues {
-  uint32_t* a;
-  uint32_t* b;
-  uint32_t* c;
-  uint32_t* touched;
-  uint32_t cap;
-};
-
-__device__ __forceinline__ uint32_t flag_or(uint8_t* base, uint32_t v, uint32_t bit) {
-  uint32_t* w = reinterpret_cast<uint32_t*>(base + (v & ~3u));
-  const int sh = (int)(v & 3u) * 8;
-  return (atomicOr(w, bit << sh) >> sh) & 0xFFu;
-}
-__device__ __forceinline__ void flag_clear(uint8_t* base, uint32_t v, uint32_t bit) {
-  uint32_t* w = reinterpret_cast<uint32_t*>(base + (v & ~3u));
-  const int sh = (int)(v & 3u) * 8;
-  atomicAnd(w, ~(bit << sh));
-}
-
-// Address spaces by type inside the searches: the pointers arrive through a function boundary as generic ones, and a
-// generic (flat) access counts on the LDS counter as well as on the vector-memory one -- an LDS read between two of them
-// would wait for the first to return.  With the address space in the type the loads are global_load / ds_read and the
-// stages below really overlap.
-#define KH_AS_GLOBAL __attribute__((address_space(1)))
-#define KH_AS_LDS __attribute__((address_space(3)))
-typedef KH_AS_GLOBAL uint32_t gu32_t;
-typedef KH_AS_GLOBAL float gf32_t;
-__device__ __forceinline__ uint32_t gld_l2(const gu32_t* p) {       // agent-scope load: the word is modified by L2 atomics
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint32_t gflag_or(gu32_t* qs, uint32_t v, uint32_t bit) {
-  const int sh = (int)(v & 3u) * 8;
-  return (__hip_atomic_fetch_or(qs + (v >> 2), bit << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> sh) & 0xFFu;
-}
-__device__ __forceinline__ void gflag_clear(gu32_t* qs, uint32_t v, uint32_t bit) {
-  const int sh = (int)(v & 3u) * 8;
-  __hip_atomic_fetch_and(qs + (v >> 2), ~(bit << sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The 27 words around voxel u of a whole-volume u32 / f32 array as nine rows of three consecutive words:
-// w[(dx + 1) + 3 * ((dy + 1) + 3 * (dz + 1))] = a[u + dx + sx * dy + sxy * dz].  A row outside the volume reads u's own row (its
-// neighbours are in nobody's mask); a row that starts one word before the array or ends one behind it is read one word further in
-// and shifted (the missing word belongs to a neighbour outside the volume).  nvox >= 3.
-typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
-typedef u32x3_t u32x3_a4_t __attribute__((aligned(4)));
-__device__ __forceinline__ void rows27_base(uint32_t nvox, int sx, int sxy, int sy, int sz, uint32_t u, int y, int z, uint32_t (&bc)[9],
-                                            int (&sh)[9]) {
-#pragma unroll
-  for (int r = 0; r < 9; r++) {
-    const int dy = r % 3 - 1, dz = r / 3 - 1;
-    const bool in = (unsigned)(y + dy) < (unsigned)sy && (unsigned)(z + dz) < (unsigned)sz;
-    const long long base = (long long)u + (in ? dy * sx + dz * sxy : 0) - 1;
-    const long long hi = nvox >= 3u ? (long long)nvox - 3 : 0;       // (arrays of fewer than three words carry padding: include/kimi_hip.h)
-    const long long c = base < 0 ? 0 : (base > hi ? hi : base);
-    bc[r] = (uint32_t)c;
-    sh[r] = (int)(base - c);
-  }
-}
-__device__ __forceinline__ void rows27_shift(const u32x3_t (&t)[9], const int (&sh)[9], uint32_t (&w)[27]) {
-#pragma unroll
-  for (int r = 0; r < 9; r++) {
-    w[3 * r + 0] = sh[r] > 0 ? t[r].y : t[r].x;                       // (sh < 0: the word in front of the array -- never used)
-    w[3 * r + 1] = sh[r] > 0 ? t[r].z : (sh[r] < 0 ? t[r].x : t[r].y);
-    w[3 * r + 2] = sh[r] < 0 ? t[r].y : t[r].z;                       // (sh > 0: the word behind the array -- never used)
-  }
-}
-// words that memory-side atomics change: past the vector cache (sc1).  The nine loads and their wait are ONE asm statement, so the
-// compiler never sees a register that is still in flight; the wait also covers the loads it has issued itself just before.
-__device__ __forceinline__ void rows27_sc1(const KH_AS_GLOBAL uint32_t* a, uint32_t nvox, int sx, int sxy, int sy, int sz, uint32_t u,
-                                           int y, int z, uint32_t (&w)[27]) {
-  uint32_t bc[9];
-  int sh[9];
-  rows27_base(nvox, sx, sxy, sy, sz, u, y, z, bc, sh);
-  u32x3_t t[9];
-  asm volatile(
-      "global_load_dwordx3 %0, %9, off sc1\n\t"
-      "global_load_dwordx3 %1, %10, off sc1\n\t"
-      "global_load_dwordx3 %2, %11, off sc1\n\t"
-      "global_load_dwordx3 %3, %12, off sc1\n\t"
-      "global_load_dwordx3 %4, %13, off sc1\n\t"
-      "global_load_dwordx3 %5, %14, off sc1\n\t"
-      "global_load_dwordx3 %6, %15, off sc1\n\t"
-      "global_load_dwordx3 %7, %16, off sc1\n\t"
-      "global_load_dwordx3 %8, %17, off sc1\n\t"
-      "s_waitcnt vmcnt(0)"
-      : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]), "=&v"(t[8])
-      : "v"(a + bc[0]), "v"(a + bc[1]), "v"(a + bc[2]), "v"(a + bc[3]), "v"(a + bc[4]), "v"(a + bc[5]), "v"(a + bc[6]), "v"(a + bc[7]),
-        "v"(a + bc[8])
-      : "memory");
-  rows27_shift(t, sh, w);
-}
-// words only plain stores of this workgroup change (the weight field: rails are zeroed between the searches)
-__device__ __forceinline__ void rows27_plain(const KH_AS_GLOBAL float* a, uint32_t nvox, int sx, int sxy, int sy, int sz, uint32_t u, int y,
-                                             int z, float (&w)[27]) {
-  uint32_t bc[9];
-  int sh[9];
-  rows27_base(nvox, sx, sxy, sy, sz, u, y, z, bc, sh);
-  u32x3_t t[9];
-#pragma unroll
-  for (int r = 0; r < 9; r++) t[r] = *(const KH_AS_GLOBAL u32x3_a4_t*)((const KH_AS_GLOBAL uint32_t*)a + bc[r]);
-  uint32_t wu[27];
-  rows27_shift(t, sh, wu);
-#pragma unroll
-  for (int i = 0; i < 27; i++) w[i] = __uint_as_float(wu[i]);
-}
-
-// LDS scratch of a search (north_star: "frontier relaxation with LDS bucket queues and wave-ballot compaction"): KH_SSSP_LDS_BYTES
-// per thread of the workgroup, laid out as
-//   key[H], val[H]   the COMBINE TABLE of a batch of frontier voxels: open addressing on the voxel index, val = the smallest
-//                    fl(d[u] + w) any frontier voxel of the batch offers the voxel (LDS atomic min).  A batch relaxes into the
-//                    table, a barrier, then every occupied slot is flushed by ONE thread: it is the only writer of dist[v], of
-//                    v's membership byte and of v's list entries, so the searches issue NO global atomic (every global atomic
-//                    on gfx950 is a fabric round trip that drops its line from the L2: DESIGN.md r6-1).
-//   qa[NQ], qb[NQ]   the heads of the two near work lists (bucket "below T" being processed / being built); entries from NQ on
-//                    overflow to the label's lists in HBM at the same index.  The far bucket stays in HBM (it is split by a
-//                    streaming pass).
-// List slots are handed out per wave: a ballot of the lanes that append, ONE LDS atomic add by the first of them, a prefix
-// population count for the others.
-#define KH_SSSP_LDS_BYTES 48u   /* per thread: H = 4 slots of 8 bytes, NQ = 2 + 2 entries of 4 bytes */
-static constexpr uint32_t SSSP_EMPTY = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uintptr_t uni64(uintptr_t v) { return ((uintptr_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
-typedef KH_AS_GLOBAL uint8_t gu8_t;
-__device__ __forceinline__ uint32_t gld8_l2(const gu8_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void gst8_l2(gu8_t* p, uint32_t v) { __hip_atomic_store(p, (uint8_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// slot of this lane among the lanes of its wave with p set (all lanes of the wave call this): base from one LDS atomic
-__device__ __forceinline__ uint32_t wave_slot(bool p, KH_AS_LDS uint32_t* counter, int lane) {
-  const unsigned long long m = __builtin_amdgcn_ballot_w64(p);
-  if (m == 0ull) return 0u;
-  const int leader = __ffsll((long long)m) - 1;
-  uint32_t base = 0u;
-  if (lane == leader) base = __hip_atomic_fetch_add(counter, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-__device__ __forceinline__ bool sssp_offer(KH_AS_LDS uint32_t* key, KH_AS_LDS uint32_t* val, uint32_t hmask, int hshift, uint32_t v,
-                                           uint32_t nb) {
-  uint32_t s = (v * 0x9E3779B1u) >> hshift;
-#pragma unroll 1
-  for (int t = 0; t < 12; t++) {
-    uint32_t seen = SSSP_EMPTY;
-    __hip_atomic_compare_exchange_strong(key + s, &seen, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (seen == SSSP_EMPTY || seen == v) {
-      __hip_atomic_fetch_min(val + s, nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      return true;
-    }
-    s = (s + 1u) & hmask;
-  }
-  return false;       // the neighbourhood of the slot is full: the frontier voxel is relaxed again after the flush
-}
-
-// MODE 0: EDF (edge length by direction).  MODE 1: railroad (cost = pdrf of the entered voxel, rails
-// absorb, stops once everything at or below the nearest rail is final).  MODE 2: parental field
-// (trace.py:155, fix_branching=False): field costs, no rails, runs to completion.
-// On return distances below the final threshold are exact (ctl->best_rail set for MODE 1).
-// lds / lds_bytes: the workgroup's search scratch, >= KH_SSSP_LDS_BYTES * blockDim.x bytes, 4-byte aligned.
-template <int MODE>
-__device__ __attribute__((noinline)) void sssp(const Geometry& g_, const uint32_t* __restrict__ nbrmask_, const float* __restrict__ wfield_,
-                     float* dist_, uint8_t* qstate_, uint32_t source, Queues q, Ctl* ctl_, float delta_floor,
-                     unsigned char* lds_, uint32_t lds_bytes, uint32_t preseeded_far = 0) {
-  constexpr bool RAIL = MODE == 1;
-  constexpr bool FIELD = MODE != 0;  // MODE 2: dijkstra3d.parental_field -- field weights, no rails, runs to completion
-  const int tid = threadIdx.x;
-  const int nthr = blockDim.x, nwav = nthr >> 6;
-  const int lane = tid & 63, wave = tid >> 6;
-  // The arguments of a function that is not a kernel arrive in VECTOR registers, uniform or not: eight 64-bit pointers and every
-  // address derived from them would live in VGPR pairs.  Read back through lane 0 they are scalars again.
-  const KH_AS_LDS Geometry* g = (const KH_AS_LDS Geometry*)(uintptr_t)uni32((uint32_t)(uintptr_t)(const KH_AS_LDS Geometry*)&g_);
-  KH_AS_LDS Ctl* ctl = (KH_AS_LDS Ctl*)(uintptr_t)uni32((uint32_t)(uintptr_t)(KH_AS_LDS Ctl*)ctl_);
-  const gu32_t* nbrmask = (const gu32_t*)uni64((uintptr_t)nbrmask_);
-  const gf32_t* wfield = (const gf32_t*)uni64((uintptr_t)wfield_);
-  gu32_t* dist = (gu32_t*)uni64((uintptr_t)dist_);                   // float bit patterns (non-negative: ordered like unsigned)
-  gu8_t* qs8 = (gu8_t*)uni64((uintptr_t)qstate_);                    // membership bytes: bit 0 near list being built, bit 1 far list
-  q.cap = uni32(q.cap);
-  gu32_t* cur = (gu32_t*)uni64((uintptr_t)q.a);
-  gu32_t* next = (gu32_t*)uni64((uintptr_t)q.b);
-  gu32_t* far = (gu32_t*)uni64((uintptr_t)q.c);
-  gu32_t* touched = (gu32_t*)uni64((uintptr_t)q.touched);
-  source = uni32(source);
-  lds_bytes = uni32(lds_bytes);
-  delta_floor = __uint_as_float(uni32(__float_as_uint(delta_floor)));
-  lds_ = (unsigned char*)(uintptr_t)uni32((uint32_t)(uintptr_t)(KH_AS_LDS unsigned char*)lds_);
-  uint32_t H = 1u;
-  while (H * 24u <= lds_bytes) H <<= 1;                              // the largest power of two with 12 H <= lds_bytes
-  const uint32_t NQ = H >> 1, hmask = H - 1u;
-  const int hshift = __clz((int)H) + 1;
-  KH_AS_LDS uint32_t* key = (KH_AS_LDS uint32_t*)(uintptr_t)lds_;
-  KH_AS_LDS uint32_t* val = key + H;
-  KH_AS_LDS uint32_t* curL = val + H;
-  KH_AS_LDS uint32_t* nextL = curL + NQ;
-  float T = RAIL ? 1e-45f : delta_floor;
-  for (uint32_t s = tid; s < H; s += nthr) { key[s] = SSSP_EMPTY; val[s] = 0xFFFFFFFFu; }
-  if (tid == 0) {
-    ctl->n_cur = 1; ctl->n_next = 0; ctl->n_far = preseeded_far; ctl->n_far2 = 0;  // far list q.c may hold seeds
-    ctl->n_touched = 0;
-    ctl->best_rail = NONE64;
-    ctl->retry[0] = ctl->retry[1] = 0u;
-    curL[0] = source;
-    __hip_atomic_store(dist + source, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (RAIL) { touched[0] = source; ctl->n_touched = 1; }
-  }
-  __syncthreads();
-  const int gsx = g->sx, gsxy = g->sxy, gsy = g->sy, gsz = g->sz;
-  const uint32_t nvox = (uint32_t)gsxy * (uint32_t)gsz;
-  uint32_t par = 0u;
-  for (;;) {
-    // ---- near phase: label-correct everything below T
-    for (;;) {
-      const uint32_t n = ctl->n_cur;
-      if (n == 0) break;
-      // ONE THREAD PER FRONTIER VOXEL, a batch of blockDim.x voxels at a time.  A thread reads its voxel's mask and the 27 distances
-      // around it as nine rows of three consecutive words (past the vector cache) -- with a weight field its 27 weights the same
-      // way -- in ONE round trip whose addresses depend on nothing but the voxel; every edge that lowers a distance is offered to
-      // the combine table; after the barrier the table is flushed (see above).
-      for (uint32_t base = 0; base < n; base += (uint32_t)nthr) {
-        const uint32_t i = base + (uint32_t)tid;
-        bool pending = i < n;
-        const uint32_t u = pending ? (i < NQ ? curL[i] : cur[i]) : source;
-        const uint32_t zz = u / (uint32_t)gsxy, rr = u - zz * (uint32_t)gsxy, yy = rr / (uint32_t)gsx;
-        if (pending) gst8_l2(qs8 + u, gld8_l2(qs8 + u) & ~1u);       // out of the near list (the only thread that holds u)
-        for (;;) {
-          if (pending) {
-            const uint32_t nm = nbrmask[u];
-            float wr[27];
-            if (FIELD) rows27_plain(wfield, nvox, gsx, gsxy, gsy, gsz, u, (int)yy, (int)zz, wr);
-            uint32_t dr[27];
-            rows27_sc1(dist, nvox, gsx, gsxy, gsy, gsz, u, (int)yy, (int)zz, dr);
-            const float du = __uint_as_float(dr[13]);
-            bool failed = false;
-#pragma unroll
-            for (int k = 0; k < 26; k++) {
-              int dx, dy, dz;
-              dir_delta(k, dx, dy, dz);
-              const int idx = (dx + 1) + 3 * ((dy + 1) + 3 * (dz + 1));
-              const float wn = FIELD ? wr[idx] : g->w[k];
-              const uint32_t nb = __float_as_uint(du + wn);
-              // distances only go down, so an edge that cannot lower dist[v] now never will
-              if (((nm >> k) & 1u) && nb < dr[idx])
-                failed |= !sssp_offer(key, val, hmask, hshift, u + (uint32_t)(dx + gsx * dy + gsxy * dz), nb);
-            }
-            pending = failed;
-            if (failed) ctl->retry[par] = 1u;
-          }
-          __syncthreads();
-          // ---- flush: one thread per occupied slot
-          for (uint32_t s = (uint32_t)tid; s < H; s += (uint32_t)nthr) {
-            const uint32_t v = key[s];
-            const bool occ = v != SSSP_EMPTY;
-            uint32_t nd = 0u, old = 0u, q8 = 0u;
-            float wv = 1.0f;
-            if (occ) {
-              nd = val[s];
-              key[s] = SSSP_EMPTY;
-              val[s] = 0xFFFFFFFFu;
-              if (RAIL) { old = gld_l2(dist + v); wv = wfield[v]; }
-              q8 = gld8_l2(qs8 + v);
-              __hip_atomic_store(dist + v, nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            const float ndf = __uint_as_float(nd);
-            const bool rail = RAIL && occ && wv == 0.0f;            // a rail: absorbing
-            if (rail) __hip_atomic_fetch_min(&ctl->best_rail, pack(ndf, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const bool t_touch = RAIL && occ && old == INF_BITS;
-            const bool t_next = occ && !rail && ndf < T && !(q8 & 1u);
-            const bool t_far = occ && !rail && !(ndf < T) && !(q8 & 2u);
-            if (t_next | t_far) gst8_l2(qs8 + v, q8 | (t_next ? 1u : 2u));
-            if (RAIL) {
-              const uint32_t p = wave_slot(t_touch, &ctl->n_touched, lane);
-              if (t_touch) {
-                if (p < q.cap) touched[p] = v;
-                else __hip_atomic_fetch_or(&ctl->status, (uint32_t)KH_ST_QUEUE_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              }
-            }
-            {
-              const uint32_t p = wave_slot(t_next, &ctl->n_next, lane);
-              if (t_next) {
-                if (p < NQ) nextL[p] = v;
-                else if (p < q.cap) next[p] = v;
-                else __hip_atomic_fetch_or(&ctl->status, (uint32_t)KH_ST_QUEUE_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              }
-            }
-            {
-              const uint32_t p = wave_slot(t_far, &ctl->n_far, lane);
-              if (t_far) {
-                if (p < q.cap) far[p] = v;
-                else __hip_atomic_fetch_or(&ctl->status, (uint32_t)KH_ST_QUEUE_OVERFLOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              }
-            }
-          }
-          const bool again = ctl->retry[par] != 0u;                  // (stable since the barrier above)
-          if (tid == 0) {
-            ctl->retry[par ^ 1u] = 0u;                               // (nobody reads or sets the other word before the next barrier)
-            if (again) ctl->n_retries++;
-          }
-          par ^= 1u;
-          __syncthreads();
-          if (!again) break;
-        }
-      }
-      if (tid == 0) {
-        ctl->n_cur = ctl->n_next < q.cap ? ctl->n_next : q.cap;
-        ctl->n_next = 0;
-        if (ctl->n_far > q.cap) ctl->n_far = q.cap;
-        if (ctl->n_cur > NQ) ctl->n_spills++;                          // the next round reads entries from HBM
-      }
-      { gu32_t* t = cur; cur = next; next = t; }
-      { KH_AS_LDS uint32_t* t = curL; curL = nextL; nextL = t; }
-      __syncthreads();
-    }
-    // ---- every voxel with d < T is final now
-    float tcap = KH_INF;
-    if (RAIL) {
-      const unsigned long long br = ctl->best_rail;
-      if (br != NONE64) {
-        const float D = __uint_as_float((uint32_t)(br >> 32));
-        if (D < T) break;
-        tcap = next_up(D);
-      }
-    }
-    const uint32_t nfar = ctl->n_far;
-    if (nfar == 0) break;
-    // pass 1: min / mean of the far entries (current distances)
-    float mn = KH_INF, sm = 0.0f;
-    uint32_t cnt = 0;
-    for (uint32_t i = tid; i < nfar; i += nthr) {
-      const float d = __uint_as_float(gld_l2(dist + far[i]));
-      mn = fminf(mn, d); sm += d; cnt++;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mn = fminf(mn, __shfl_xor(mn, o));
-      sm += __shfl_xor(sm, o);
-      cnt += __shfl_xor(cnt, o);
-    }
-    if (lane == 0) { ctl->red_min[wave] = mn; ctl->red_sum[wave] = sm; ctl->red_cnt[wave] = cnt; }
-    __syncthreads();
-    mn = ctl->red_min[0]; sm = ctl->red_sum[0]; cnt = ctl->red_cnt[0];
-    for (int i = 1; i < nwav; i++) { mn = fminf(mn, ctl->red_min[i]); sm += ctl->red_sum[i]; cnt += ctl->red_cnt[i]; }
-    if (RAIL && !(mn < tcap)) break;  // nothing left at or below the nearest rail
-    const float mean = sm / (float)cnt;
-    float step = 0.5f * (mean - mn);
-    if (!(step > delta_floor)) step = delta_floor;
-    float Tn = mn + step;
-    if (!(Tn > mn)) Tn = next_up(mn);
-    if (Tn < T) Tn = T;
-    if (Tn > tcap) Tn = tcap;
-    T = Tn;
-    // pass 2: split far -> cur (d < T) + compacted far (into the free `next` buffer); every entry has one thread, which is the
-    // only writer of the voxel's membership byte
-    for (uint32_t base = 0; base < nfar; base += (uint32_t)nthr) {
-      const uint32_t i = base + (uint32_t)tid;
-      const bool have = i < nfar;
-      const uint32_t v = have ? far[i] : source;
-      const float d = __uint_as_float(gld_l2(dist + v));
-      const uint32_t q8 = gld8_l2(qs8 + v) & ~2u;
-      const bool near = have && d < T;
-      const bool t_cur = near && !(q8 & 1u);
-      const bool t_far = have && !near;
-      if (have) gst8_l2(qs8 + v, q8 | (t_cur ? 1u : 0u) | (t_far ? 2u : 0u));
-      const uint32_t pc = wave_slot(t_cur, &ctl->n_cur, lane);
-      if (t_cur) { if (pc < NQ) curL[pc] = v; else cur[pc] = v; }    // pc < nfar <= cap
-      const uint32_t pf = wave_slot(t_far, &ctl->n_far2, lane);
-      if (t_far) next[pf] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      ctl->n_far = ctl->n_far2; ctl->n_far2 = 0;
-      ctl->n_splits++;
-      if (ctl->n_cur > NQ) ctl->n_spills++;
-    }
-    gu32_t* t = far; far = next; next = t;
-    __syncthreads();
-  }
-  __syncthreads();
-}
-
-// ------------------------------------------------------------------------------------------------
-// One distance-field search of ONE label by its workgroup (dijkstra3d.euclidean_distance_field, kimimaro/trace.py:139-145, 302-307):
-// the field over the label's voxels from `source`, +inf before; task.max_loc / max_val = the farthest voxel (ties -> smallest
-// linear index); mode 1 (find_root): task.root = that voxel.  Out of line: the batch kernel and the path kernel share it.
-__device__ __attribute__((noinline)) void edf_label(Ctl* ctl_, kh_label_t* task, int mode, const uint32_t* __restrict__ list, uint32_t nf,
-                                                    const uint32_t* __restrict__ nbrmask, float* field, uint8_t* qstate, Queues q,
-                                                    float delta_floor, uint32_t source, unsigned char* lds, uint32_t lds_bytes) {
-  Ctl& ctl = *ctl_;
-  const Geometry& g = ctl.g;
-  const int tid = threadIdx.x;
-  const int nthr = blockDim.x, nwav = nthr >> 6;
-  const int lane = tid & 63, wave = tid >> 6;
-  for (uint32_t i = tid; i < nf; i += nthr) st_f32_l2(&field[list[i]], KH_INF);
-  __syncthreads();
-  uint32_t seeded = 0;
-  if (mode == 2 && task->fsr > 0.0f) {
-    // free_space_radius (trace.py:134,142; dijkstra3d source absent, restated in oracle ko_edf): label
-    // voxels closer than the radius in a straight line get that distance and seed the search (far list).
-    const float fsr = task->fsr;
-    const uint32_t sxu = (uint32_t)g.sx, sxy = (uint32_t)g.sxy;
-    const uint32_t z0 = source / sxy, r0 = source - z0 * sxy, y0 = r0 / sxu, x0 = r0 - y0 * sxu;
-    if (tid == 0) ctl.u0 = 0;
-    __syncthreads();
-    for (uint32_t i = tid; i < nf; i += nthr) {
-      const uint32_t v = list[i];
-      if (v == source) continue;
-      const uint32_t z = v / sxy, r = v - z * sxy, y = r / sxu, x = r - y * sxu;
-      const float a = g.wx * (float)((int)x - (int)x0), b = g.wy * (float)((int)y - (int)y0), c = g.wz * (float)((int)z - (int)z0);
-      float s2 = a * a;
-      const float t2 = b * b, u2 = c * c;
-      s2 = s2 + t2;
-      s2 = s2 + u2;
-      const float sd = sqrtf(s2);
-      if (sd < fsr) {
-        st_f32_l2(&field[v], sd);
-        flag_or(qstate, v, 2u);
-        const uint32_t p = atomicAdd(&ctl.u0, 1u);
-        q.c[p] = v;  // p < nf <= cap
-      }
-    }
-    __syncthreads();
-    seeded = ctl.u0;
-  }
-  sssp<0>(ctl.g, nbrmask, nullptr, field, qstate, source, q, &ctl, delta_floor, lds, lds_bytes, seeded);
-  // farthest voxel: max finite distance, ties -> smallest linear index
-  unsigned long long best = 0;
-  for (uint32_t i = tid; i < nf; i += nthr) {
-    const uint32_t v = list[i];
-    const uint32_t b = __float_as_uint(ld_f32_l2(&field[v]));
-    if (b == INF_BITS) continue;
-    const unsigned long long key = ((unsigned long long)b << 32) | (0xFFFFFFFFu - v);
-    if (key > best) best = key;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long ob = __shfl_xor(best, o);
-    if (ob > best) best = ob;
-  }
-  if (lane == 0) ctl.red64[wave] = best;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < nwav; i++) if (ctl.red64[i] > best) best = ctl.red64[i];
-    const uint32_t loc = 0xFFFFFFFFu - (uint32_t)best;
-    task->max_loc = loc;
-    task->max_val = __uint_as_float((uint32_t)(best >> 32));
-    if (mode == 1) task->root = loc;
-    ctl.red64[0] = best;          // (for the callers' other threads: the record itself was written by this thread only)
-  }
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(1024) void edf_batch_kernel(kh_label_t* tasks, int mode, const uint32_t* __restrict__ lists,
                                                         const uint32_t* __restrict__ nbrmask, Geometry g, float* field,
@@ -529,711 +57,47 @@ __global__ __launch_bounds__(1024) void edf_batch_kernel(kh_label_t* tasks, int 
   const uint32_t source = (mode == 2) ? task->root : task->source;
   if (tid == 0) { ctl.status = 0; ctl.n_retries = ctl.n_spills = ctl.n_splits = 0; ctl.g = g; }
   __syncthreads();
-  Queues q;
-  q.cap = task->q_capacity;
-  q.a = queues + (uint64_t)task->q_offset * 4;
-  q.b = q.a + q.cap;
-  q.c = q.b + q.cap;
-  q.touched = q.c + q.cap;
+  const Queues q = task_queues(task, queues);
   edf_label(&ctl, task, mode, lists + task->list_offset, task->count, nbrmask, field, qstate, q, delta_floor, source, search_lds,
             KH_SSSP_LDS_BYTES * blockDim.x);
   if (tid == 0) {
     task->status |= ctl.status;
-    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+    search_stats(task, ctl);
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// The invalidation heap: an exact emulation of std::priority_queue<HeapDistanceNode, vector, Compare>
-// with Compare = `t1.dist >= t2.dist` (dijkstra_invalidation.hpp:233-237, 262-264) as libstdc++
-// implements it (bits/stl_heap.h), because the pop order among equal keys decides which source owns
-// a voxel.  The array layout after every operation is identical to libstdc++'s:
-//   push  = __push_heap: the new key climbs over every ancestor with key >= it.  The ancestors of the
-//           new leaf are known up front, so the wave loads them all at once (lane g = generation g),
-//           a ballot gives the climb length and the lanes shift the chain down in one step.
-//   pop   = __pop_heap/__adjust_heap: libstdc++ walks the hole to a leaf along the smaller child
-//           (ties: left) and then pushes the last element up again.  Because keys never decrease
-//           from parent to child this lands exactly where the text-book early-exit sift-down lands
-//           (verified against the libstdc++ form in oracle/ tests), so the wave descends 6 levels
-//           per memory round trip: 126 speculative child nodes are fetched by the 64 lanes, the path
-//           is resolved from registers, and the nodes on it are moved up in one parallel step.
-// Nodes are 16-byte records {key bits, voxel, source index, -} in the label's slice of HBM scratch, so
-// a node is one dwordx4 load or store.  Keys are non-negative floats: they are compared as their bit
-// patterns (unsigned), which lets "ties go left" be written as k < sibling + (1 on left lanes).
-// LDS mirrors, both ways.  A write-through mirror of WHOLE NODES of heap levels 0-12 was tried twice in the first rounds
-// (one volume alone) and measured 10-15 % slower: alone the pop's global trips hit the L2 and the pop is bound by the
-// instruction issue of its single wave.  The KEY mirror of levels 7-10 below is a different trade (4 bytes per slot, one
-// global trip less per pop).  Measured with twenty volumes in flight (BENCH_NOTES.md, "Heap key mirror"): bit exact, the longest
-// chain under load 11 789 -> 11 354 Mcyc (median of the lanes, -3.7 %), the step time 370.1 -> 368.4 ms (medians of three, the
-// parent's own spread 13.6 ms): NOT a gain beyond the spread -- the trip it removes is not what doubles the chain under load.
-// No new spills in invalidate_ball, +57 instructions.  -DKH_HEAP_MIRROR_LEVELS=0 is the code without it.
-// a native LLVM vector (HIP's uint4 is a struct around a union, which ends up in scratch memory here)
-typedef uint32_t hnode_t __attribute__((ext_vector_type(4)));
-// LDS pointers keep their address space in the type, so LDS and HBM accesses can never be merged into flat_* ones
-typedef __attribute__((address_space(3))) hnode_t lds_hnode_t;
-
-// Heap slots 0..TOP-1 live in LDS and nowhere else; slots >= TOP live in the label's slice of HBM scratch.
-// TOPL = 1: the root and the first 6-level chunk under it (127 slots, 2 KiB) -- every label affords that.
-// TOPL = 2: two chunks (8191 slots, 128 KiB): one such workgroup fits on a CU, so it is reserved for the few
-// largest labels, whose sequential chain is the critical path of the whole launch.  Every pop starts in the
-// LDS part, so the top read and the first TOPL chunks cost LDS round trips instead of L2 ones.
-//
-// The key mirror (TOPL = 1 only).  Behind the 130 LDS nodes lie the KEYS of the next KH_HEAP_MIRROR_LEVELS heap levels (default 4:
-// levels 7-10, slots 127..2046, 7 680 B).  The nodes of those slots stay in HBM and HBM is the truth; every store to such a slot
-// writes its key through (heap_store, the pop's moves).  A pop decides its path through those levels from the keys alone and
-// fetches the (at most 4) whole nodes on it together with the 6 levels under them: a heap below 131 072 nodes costs a pop one
-// global round trip instead of two.  The mirror is never initialised: a slot is read only below `len`, and it was written when
-// it was filled.  The bytes are the workgroup's dynamic LDS, which the sweep and the searches use between the heap's calls.
-// 0 compiles the stage out.
-#ifndef KH_HEAP_MIRROR_LEVELS
-#define KH_HEAP_MIRROR_LEVELS 4
-#endif
-static_assert(KH_HEAP_MIRROR_LEVELS >= 0 && KH_HEAP_MIRROR_LEVELS <= 5, "the mirror stage resolves at most 62 nodes (one per lane)");
-typedef __attribute__((address_space(3))) uint32_t lds_key_t;
-
-template <int TOPL_>
-struct Heap {
-  static constexpr int TOPL = TOPL_;
-  static constexpr uint32_t TOP = TOPL_ == 1 ? 127u : 8191u;
-  static constexpr int MIRL = TOPL_ == 1 ? KH_HEAP_MIRROR_LEVELS : 0;     // mirrored levels under the LDS part
-  static constexpr uint32_t MIR_END = ((TOP + 1u) << MIRL) - 1u;          // slots TOP .. MIR_END-1 have their key in LDS too
-  static constexpr size_t LDS_BYTES = (size_t)(TOP + 3u) * 16u + (size_t)(MIR_END - TOP) * 4u;
-  // pop: nested 6-level chunks (the LDS ones included).  32-bit index math needs every hole at level <= 24:
-  // without the mirror the holes sit at levels 0, 6, .., 24 (30 levels), with it at 0, 6 | 6+MIRL, .., 18+MIRL (<= 29 levels)
-  static constexpr int CHUNKS = MIRL ? 4 : 5;
-  static constexpr uint32_t MAX_N = MIRL ? (1u << (6 * CHUNKS + MIRL + 1)) - 1u : 0x7FFFFFFFu;   // the nodes a pop can descend through
-  hnode_t* node;   // HBM scratch of this label (L2 resident in practice); slots < TOP unused
-  lds_hnode_t* top;  // LDS, TOP + 3 entries (the last LDS chunk's lanes 62/63 read two slots past the end); then the key mirror
-  uint32_t cap, n;
-  __device__ __forceinline__ lds_key_t* mir() const { return (lds_key_t*)(top + (TOP + 3u)); }   // key of slot i: mir()[i - TOP]
-  // per-lane constants of the 126-node speculative sub-tree (children of node m: 2m+2, 2m+3; parent of
-  // m >= 2: (m-2)>>1).  Lane l holds node m = l ("slot 0", depths 1..6) and m = l+64 ("slot 1", depth 6).
-  unsigned long long am0, am1;  // slot-0 ballot bits of the node's ancestors (am0 including itself)
-  uint32_t sh0, j0, j1;         // heap index of my slot-0 node = ((hole+1) << sh0) - 1 + j0, slot 1: << 6, + j1
-  uint32_t lf;                  // 1 on even lanes (left children), 0 on odd lanes
-};
-
-__device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// value of lane l^1 (the sibling node): DPP quad_perm [1,0,3,2], no LDS crossbar round trip
-__device__ __forceinline__ uint32_t sibling_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);
-}
-
-template <class H>
-__device__ __forceinline__ void heap_init_lane(H& h, int lane) {
-  unsigned long long a0 = 0, a1 = 0;
-  for (int m = lane; ; m = (m - 2) >> 1) { a0 |= 1ull << m; if (m < 2) break; }
-  if (lane + 64 < 126) for (int m = (lane + 62) >> 1; ; m = (m - 2) >> 1) { a1 |= 1ull << m; if (m < 2) break; }
-  h.am0 = a0;
-  h.am1 = a1;
-  const int d0 = 31 - __clz(lane + 2);
-  h.sh0 = (uint32_t)d0;
-  h.j0 = (uint32_t)(lane + 2 - (1 << d0));
-  h.j1 = (uint32_t)(lane + 2);
-  h.lf = (lane & 1) ? 0u : 1u;
-}
-
-// store of a whole node to slot i, wherever it lives (the mirror's key written through)
-template <class H>
-__device__ __forceinline__ void heap_store(const H& h, uint32_t i, hnode_t v) {
-  if (i < H::TOP) h.top[i] = v;
-  else {
-    h.node[i] = v;
-    if constexpr (H::MIRL > 0) { if (i < H::MIR_END) h.mir()[i - H::TOP] = v.x; }
-  }
-}
-
-// all 64 lanes of the wave call this with uniform arguments.  One memory round trip: lane g loads
-// the whole node of ancestor generation g+1 (from LDS or HBM, whichever holds that slot), a ballot gives
-// the climb length m (the ancestors with key >= k form a prefix because keys never decrease from parent
-// to child), lanes < m write their ancestor one generation down and lane m drops the new node into
-// generation m's slot.
-template <class H>
-__device__ __forceinline__ bool heap_push_wave(H& h, uint32_t kbits, uint32_t vox, uint32_t src, int lane) {
-  if (h.n >= h.cap) return false;
-  const uint32_t pos = h.n++;
-  const int sh = lane + 1 < 32 ? lane + 1 : 31;
-  const uint32_t q = (pos + 1u) >> sh;
-  const bool valid = (lane < 31) && q >= 1u;
-  const uint32_t ai = q - 1u;
-  hnode_t a;
-  if (pos < H::TOP) {                     // wave uniform: the whole chain is in LDS
-    a = h.top[valid ? ai : 0u];
-  } else {
-    const bool lo = !valid || ai < H::TOP;
-    const hnode_t ag = h.node[lo ? H::TOP : ai];
-    const hnode_t al = h.top[lo && valid ? ai : 0u];
-    a = lo ? al : ag;
-  }
-  const unsigned long long climb = ballot64(valid && a.x >= kbits);
-  const int m = __ffsll((long long)~climb) - 1;  // length of the leading run of set bits (lane 63 never set)
-  const uint32_t dest = ((pos + 1u) >> (lane < 31 ? lane : 31)) - 1u;  // slot of generation `lane` (lane 0: the new leaf)
-  const hnode_t fresh = {kbits, vox, src, 0u};
-  const hnode_t val = lane < m ? a : fresh;
-  if (lane <= m) heap_store(h, dest, val);
-  return true;
-}
-
-// removes the top; precondition h.n > 0.  libstdc++'s __adjust_heap walks the hole to a leaf along the
-// smaller child (ties: left) and then pushes the former last element up again; the result is: the path
-// nodes with key < last.key move up one level and `last` takes the slot of the deepest of them.
-// The wave fetches 6 levels (126 whole nodes, 2 per lane) per round trip.  A node is on the path iff it
-// and all its ancestors in the sub-tree beat their siblings: one sibling compare per lane, one ballot,
-// one mask test against the lane's constant ancestor mask.  The chunks nest (chunk c+1 runs inside
-// chunk c, which keeps its two nodes in registers) and every write is issued on the way back up, so the
-// load of `last` overlaps the whole descent.  Loads are unconditional (index clamped, key masked
-// to +inf): no divergent branches in the descent.  Chunk 0 is exactly the LDS part of the heap.
-// 32-bit index math is safe: the hole of chunk c sits at level 6c <= 24, so (hole+1) << 6 < 2^31.
-// With the key mirror (H::MIRL > 0) the keys-only stage heap_pop_mirror sits between the LDS part and the first global chunk.
-template <int C, class H>
-__device__ __forceinline__ void heap_pop_mirror(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
-                                                uint32_t& deepest, bool& found);
-template <int C, class H>
-__device__ __forceinline__ void heap_pop_chunk(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
-                                               uint32_t& deepest, bool& found) {
-  const uint32_t i0 = ((hole + 1u) << h.sh0) - 1u + h.j0;
-  const uint32_t i1 = ((hole + 1u) << 6) - 1u + h.j1;
-  const bool e0 = i0 < len, e1 = (lane < 62) && (i1 < len);
-  hnode_t n0, n1;
-  if constexpr (C < H::TOPL) { n0 = h.top[i0]; n1 = h.top[i1]; }   // an LDS chunk: i0, i1 < TOP + 3 by construction
-  else { n0 = h.node[e0 ? i0 : H::TOP]; n1 = h.node[e1 ? i1 : H::TOP]; }
-  const uint32_t k0 = e0 ? n0.x : INF_BITS, k1 = e1 ? n1.x : INF_BITS;
-  // a node beats its sibling if it is the left one and left.key <= right.key, or the right one and
-  // right.key < left.key (comp(right, left) of dijkstra_invalidation.hpp:233-237: ties go left)
-  const bool w0 = e0 & (k0 < sibling_u32(k0) + h.lf);
-  const bool w1 = e1 & (k1 < sibling_u32(k1) + h.lf);
-  const unsigned long long W0 = ballot64(w0);
-  const bool on0 = (W0 & h.am0) == h.am0;
-  const bool on1 = w1 && ((W0 & h.am1) == h.am1);
-  if constexpr (C + 1 < H::CHUNKS) {
-    // next hole = the depth-6 node of the path, if the path got that deep and that node has children
-    const unsigned long long P0 = ballot64(on0), P1 = ballot64(on1);
-    uint32_t nh = 0;
-    if (P1) nh = rdlane_u32(i1, __ffsll((long long)P1) - 1);
-    else if (P0 >> 62) nh = rdlane_u32(i0, (P0 >> 63) ? 63 : 62);
-    if (nh != 0u && 2u * nh + 1u < len) {
-      if constexpr (H::MIRL > 0 && C + 1 == H::TOPL) heap_pop_mirror<C + 1, H>(h, nh, len, vk, lane, deepest, found);
-      else heap_pop_chunk<C + 1, H>(h, nh, len, vk, lane, deepest, found);
-    }
-  }
-  // every path node with key < last.key moves to its parent's slot; `last` lands in the slot of the
-  // deepest such node (or the root).  Path keys are non-decreasing with depth.
-  const bool mv0 = on0 && k0 < vk;
-  const bool mv1 = on1 && k1 < vk;
-  const uint32_t q0 = (i0 - 1u) >> 1, q1 = (i1 - 1u) >> 1;
-  if constexpr (C < H::TOPL) {
-    if (mv0) h.top[q0] = n0;
-    if (mv1) h.top[q1] = n1;
-  } else if constexpr (C == H::TOPL && H::MIRL > 0) {
-    // the parent of this chunk's two depth-1 nodes (lanes 0, 1) is the hole: a slot of the deepest mirrored level
-    if (mv0) { h.node[q0] = n0; if (lane < 2) h.mir()[hole - H::TOP] = k0; }
-    if (mv1) h.node[q1] = n1;
-  } else if constexpr (C == H::TOPL) {
-    // the parent of this chunk's two depth-1 nodes (lanes 0, 1) is the hole: a leaf of the LDS part
-    if (mv0) { if (lane < 2) h.top[hole] = n0; else h.node[q0] = n0; }
-    if (mv1) h.node[q1] = n1;
-  } else {
-    if (mv0) h.node[q0] = n0;
-    if (mv1) h.node[q1] = n1;
-  }
-  if (!found) {
-    const unsigned long long M0 = ballot64(mv0), M1 = ballot64(mv1);
-    if (M1) { deepest = rdlane_u32(i1, __ffsll((long long)M1) - 1); found = true; }
-    else if (M0) { deepest = rdlane_u32(i0, 63 - __clzll((long long)M0)); found = true; }
-  }
-}
-
-// The keys-only stage under the hole at the last LDS level: the speculative sub-tree of MIRL levels is 2^(MIRL+1) - 2 slots (30),
-// lane l holds its node l exactly as in a chunk's slot 0.  The key comes from the mirror; sibling compare, ballot and ancestor
-// masks are the chunk's.  Then the lanes on the path fetch their whole node from HBM (the moves need {voxel, source}) -- every
-// lane loads, the others the clamp slot -- and the first global chunk starts under the hole at the deepest mirrored level: both
-// are in flight together, one round trip.  Writes on the way back up, as in a chunk.
-template <int C, class H>
-__device__ __forceinline__ void heap_pop_mirror(const H& h, uint32_t hole, uint32_t len, uint32_t vk, int lane,
-                                                uint32_t& deepest, bool& found) {
-  constexpr int NN = (2 << H::MIRL) - 2;           // nodes of the sub-tree
-  constexpr int D0 = (1 << H::MIRL) - 2;           // its first node of the deepest level
-  const uint32_t i0 = ((hole + 1u) << h.sh0) - 1u + h.j0;
-  const bool e0 = (lane < NN) && (i0 < len);
-  const uint32_t km = h.mir()[e0 ? i0 - H::TOP : 0u];
-  const uint32_t k0 = e0 ? km : INF_BITS;
-  const bool w0 = e0 & (k0 < sibling_u32(k0) + h.lf);
-  const unsigned long long W0 = ballot64(w0);
-  const bool on0 = (W0 & h.am0) == h.am0;
-  const hnode_t n0 = h.node[on0 ? i0 : H::TOP];
-  {
-    const unsigned long long PD = ballot64(on0) >> D0;
-    const uint32_t nh = PD ? rdlane_u32(i0, D0 + __ffsll((long long)PD) - 1) : 0u;
-    if (nh != 0u && 2u * nh + 1u < len) heap_pop_chunk<C, H>(h, nh, len, vk, lane, deepest, found);
-  }
-  const bool mv0 = on0 && k0 < vk;
-  const uint32_t q0 = (i0 - 1u) >> 1;
-  if (mv0) {
-    if (lane < 2) h.top[hole] = n0;      // the hole is a leaf of the LDS part
-    else { h.node[q0] = n0; h.mir()[q0 - H::TOP] = k0; }
-  }
-  if (!found) {
-    const unsigned long long M0 = ballot64(mv0);
-    if (M0) { deepest = rdlane_u32(i0, 63 - __clzll((long long)M0)); found = true; }
-  }
-}
-
-template <class H>
-__device__ __forceinline__ void heap_pop_wave(H& h, int lane) {
-  const uint32_t len = h.n - 1u;
-  h.n = len;
-  if (len == 0) return;
-  const hnode_t last = len < H::TOP ? h.top[len] : h.node[len];  // consumed only after the descent
-  uint32_t deepest = 0;
-  bool found = false;
-  if (len > 1u) heap_pop_chunk<0, H>(h, 0u, len, last.x, lane, deepest, found);
-  if (lane == 0) heap_store(h, deepest, last);
-}
-
-// wave 0 only.  Returns the number of voxels invalidated.  PROF adds the pop / push / neighbour-test
-// cycle split (s_memtime waits on the scalar memory counter, so the production kernel leaves it out).
-// Out of line, the heap record by value: the emulation is ONE chain of dependent operations per call and every instruction the
-// register allocator adds to its loops (a reloaded pointer, a lane written to a spill register) is on that chain; as a function of
-// its own it is allocated for itself (inlined, 47 spilled VGPRs of the kernel cost it 8 %).
-template <bool PROF, class H>
-__device__ __attribute__((noinline)) uint32_t invalidate_ball(const Geometry& g, const kh_label_t* task, const uint32_t* __restrict__ nbrmask,
-                                    const float* __restrict__ dbf, uint8_t* alive, const uint32_t* path, uint32_t npath,
-                                    float scale, float constant, H h, uint32_t* status, uint32_t* pushes,
-                                    unsigned long long* cyc3, const uint8_t* __restrict__ corner_gate = nullptr) {
-  const int lane = threadIdx.x & 63;
-  unsigned long long c_pop = 0, c_push = 0, c_fire = 0, tt = 0;
-  h.n = 0;
-  uint32_t npush = 0;
-  bool ovf = false;
-  for (uint32_t i = 0; i < npath; i++) {
-    if (!heap_push_wave(h, 0u, path[i], i, lane)) ovf = true;
-    npush++;
-  }
-  const uint32_t sx = (uint32_t)g.sx, sxy = (uint32_t)g.sxy;
-  const uint32_t xmin = task->xmin, xmax = task->xmax;
-  int dx, dy, dz;
-  dir_delta(lane < 26 ? lane : 0, dx, dy, dz);
-  uint32_t count = 0;
-  while (h.n > 0) {
-    const hnode_t top = h.top[0];
-    const uint32_t vox = top.y, si = top.z;
-    const uint8_t live = alive[vox];   // issued before the pop so its latency overlaps the sift-down
-    if (PROF) tt = clock64();
-    heap_pop_wave(h, lane);
-    if (PROF) c_pop += clock64() - tt;
-    if (!live) continue;
-    if (PROF) tt = clock64();
-    if (lane == 0) alive[vox] = 0;
-    count++;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    const uint32_t src = path[si];
-    float maxd = scale * dbf[src];   // skeletontricks.pyx:393-395, f32 ops
-    maxd = maxd + constant;
-    const uint32_t z = vox / sxy, r = vox - z * sxy, y = r / sx, x = r - y * sx;
-    const uint32_t oz = src / sxy, orr = src - oz * sxy, oy = orr / sx, ox = orr - oy * sx;
-    // neighbour enumeration of dijkstra_invalidation.hpp:60-124 seen from the label's bounding box:
-    // a corner entry (k >= 18) whose x step leaves the box degenerates into the yz diagonal.
-    bool want = false;
-    uint32_t q = 0;
-    float nd = 0.0f;
-    if (lane < 26) {
-      int k = lane;
-      int ex = dx;
-      const bool xout = (dx < 0 && x == xmin) || (dx > 0 && x == xmax);
-      if (xout) {
-        if (lane >= 18) { ex = 0; k = 10 + (dy > 0 ? 2 : 0) + (dz > 0 ? 1 : 0); }
-        else k = -1;
-      }
-      // with a voxel_connectivity_graph a degenerate corner entry is gated by the corner's bit, not the diagonal's
-      const bool open = k < 0 ? false
-                      : (xout && lane >= 18 && corner_gate != nullptr) ? ((corner_gate[vox] >> (lane - 18)) & 1u) != 0u
-                                                                       : ((nbrmask[vox] >> k) & 1u) != 0u;
-      if (open) {
-        q = vox + (uint32_t)(ex + (int)sx * dy + (int)sxy * dz);
-        if (alive[q]) {
-          const int qx = (int)x + ex, qy = (int)y + dy, qz = (int)z + dz;
-          const float a = g.wx * (float)(qx - (int)ox);
-          const float b = g.wy * (float)(qy - (int)oy);
-          const float c = g.wz * (float)(qz - (int)oz);
-          float s = a * a;
-          const float t = b * b;
-          const float u = c * c;
-          s = s + t;
-          s = s + u;
-          nd = sqrtf(s);
-          want = nd < maxd;
-        }
-      }
-    }
-    unsigned long long m = ballot64(want);
-    if (PROF) { c_fire += clock64() - tt; tt = clock64(); }
-    const uint32_t ndb = __float_as_uint(nd);
-    // The pushes of one fired voxel go to consecutive leaves, in direction order.  About three quarters of them do
-    // not climb (measured: 76 % on the largest label of the bench volume): such a push writes its own leaf and
-    // nothing else, and whether it climbs depends on its parent only.  So every pending lane looks at the parent
-    // of the leaf it would get, the leading run of non-climbing pushes is appended with one store per lane, the
-    // first climbing one goes through the ordinary push, and the rest is looked at again (its parents may have
-    // changed).  A new leaf is nobody's parent here because the heap is larger than the batch.
-    while (m) {
-      const uint32_t base = h.n;
-      const uint32_t cnt = (uint32_t)__popcll(m);
-      if (base < 64u || base + cnt > h.cap) {   // small heap (new leaves could be parents) or no room: one by one
-        const int k = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        if (!heap_push_wave(h, rdlane_u32(ndb, k), rdlane_u32(q, k), si, lane)) ovf = true;
-        npush++;
-        continue;
-      }
-      const bool mine = (m >> lane) & 1ull;
-      const uint32_t leaf = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      const uint32_t par = (leaf - 1u) >> 1;
-      const bool plo = !mine || par < H::TOP;
-      const uint32_t kg = h.node[plo ? H::TOP : par].x;
-      const uint32_t kl = h.top[plo && mine ? par : 0u].x;
-      const bool stay = mine && (plo ? kl : kg) < ndb;          // __push_heap climbs while parent.key >= key
-      const unsigned long long climbers = m & ~ballot64(stay);
-      const int c = climbers ? __ffsll((long long)climbers) - 1 : 64;   // first lane whose push climbs
-      const unsigned long long run = c < 64 ? (m & ((1ull << c) - 1ull)) : m;
-      if ((run >> lane) & 1ull) {
-        const hnode_t fresh = {ndb, q, si, 0u};
-        heap_store(h, leaf, fresh);
-      }
-      const uint32_t nrun = (uint32_t)__popcll(run);
-      h.n = base + nrun;
-      npush += nrun;
-      m &= ~run;
-      if (c < 64) {
-        m &= ~(1ull << c);
-        if (!heap_push_wave(h, rdlane_u32(ndb, c), rdlane_u32(q, c), si, lane)) ovf = true;
-        npush++;
-      }
-    }
-    if (PROF) c_push += clock64() - tt;
-  }
-  if (lane == 0) {
-    if (ovf) atomicOr(status, KH_ST_HEAP_OVERFLOW);
-    *pushes += npush;
-    if (PROF) { cyc3[0] += c_pop; cyc3[1] += c_push; cyc3[2] += c_fire; }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  return count;
-}
-
-// wave 0 only: canonical predecessor walk (oracle ko_walk).  Writes the path (start first) to out[0..];
-// returns its length (0 on failure).
-//   - normally pred(v) = the achieving neighbour (fl(d[u] + f[v]) == d[v]) with d[u] < d[v] minimising (d[u], index);
-//   - at the rail end of a railroad (f == 0) every achieving neighbour has d[u] == d[v]: smallest index;
-//   - float-absorption plateau (all achieving neighbours have d[u] == d[v]): breadth-first search over the
-//     equal-distance achieving neighbours (FIFO, neighbours in direction order) to the first voxel with a
-//     strictly smaller achieving predecessor; the BFS route is followed.  bq / bpar: scratch lists (>= Nf
-//     entries), visited marks live in bit 4 of the label's own qstate bytes.
-// With a voxel graph (kh_apply_voxel_graph) the masks are one-way: bit k of nbrmask[v] says "a step FROM v in direction k is
-// allowed".  A predecessor u of v needs the step u -> v, i.e. the bit of the OPPOSITE direction in u's word; without a graph
-// the masks are symmetric and v's own word serves (one load less per step).
-__device__ __forceinline__ bool pred_edge(const Geometry& g, const uint32_t* __restrict__ nbrmask, uint32_t v, int lane, bool graph) {
-  if (lane >= 26) return false;
-  if (!graph) return ((nbrmask[v] >> lane) & 1u) != 0u;
-  int dx, dy, dz;
-  dir_delta(lane, dx, dy, dz);
-  const uint32_t sx = (uint32_t)g.sx, sxy = (uint32_t)g.sxy;
-  const uint32_t z = v / sxy, r = v - z * sxy, y = r / sx, x = r - y * sx;
-  const int nx = (int)x + dx, ny = (int)y + dy, nz = (int)z + dz;
-  if (nx < 0 || ny < 0 || nz < 0 || nx >= g.sx || ny >= g.sy || nz >= g.sz) return false;
-  // the opposite direction: the table of common.h lists every direction next to its opposite (0/1, 2/3, ... are pairs by
-  // construction for the faces; looked up by offset for the rest)
-  int opp = 0;
-#pragma unroll
-  for (int j = 0; j < 26; j++) {
-    int ex, ey, ez;
-    dir_delta(j, ex, ey, ez);
-    if (ex == -dx && ey == -dy && ez == -dz) opp = j;
-  }
-  const uint32_t u = v + (uint32_t)g.off[lane];
-  return ((nbrmask[u] >> opp) & 1u) != 0u;
-}
-
-template <bool RAILS>
-__device__ __attribute__((noinline)) uint32_t backtrack(const Geometry& g, const uint32_t* __restrict__ nbrmask,
-                                                        const float* __restrict__ pdrf, const float* dist,
-                                                        uint32_t rail_end, uint32_t target, uint32_t* out, uint32_t cap,
-                                                        uint32_t* bq, uint32_t* bpar, uint32_t bcap, uint8_t* qstate,
-                                                        uint32_t* status, bool graph = false) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  uint32_t v = rail_end, n = 0;
-  if (lane == 0) out[0] = v;
-  n = 1;
-  while (v != target) {
-    const float dv = ld_f32_l2(&dist[v]);
-    const float fv = pdrf[v];
-    const bool at_rail_end = RAILS && v == rail_end;
-    unsigned long long key = NONE64;
-    if (pred_edge(g, nbrmask, v, lane, graph)) {
-      const uint32_t u = v + (uint32_t)g.off[lane];
-      const float fu = pdrf[u];
-      if (!RAILS || fu != 0.0f) {
-        const float du = ld_f32_l2(&dist[u]);
-        if (du != KH_INF && du + fv == dv && (at_rail_end || du < dv)) key = pack(du, u);
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long ok = __shfl_xor(key, o);
-      if (ok < key) key = ok;
-    }
-    if (key != NONE64) {
-      if (n >= cap) { if (lane == 0) atomicOr(status, KH_ST_PATH_OVERFLOW); return 0; }
-      v = (uint32_t)key;
-      if (lane == 0) out[n] = v;
-      n++;
-      continue;
-    }
-    if (at_rail_end) { if (lane == 0) atomicOr(status, KH_ST_NO_RAIL); return 0; }
-    // ---- plateau search
-    uint32_t head = 0, tail = 1, found = 0xFFFFFFFFu;
-    if (lane == 0) { bq[0] = v; bpar[0] = 0xFFFFFFFFu; qstate[v] |= 0x10; }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    while (head < tail) {
-      const uint32_t x = bq[head];
-      const float dx = ld_f32_l2(&dist[x]);
-      const float fx = pdrf[x];
-      bool strict = false, equal = false;
-      uint32_t u = 0;
-      if (pred_edge(g, nbrmask, x, lane, graph)) {
-        u = x + (uint32_t)g.off[lane];
-        const float fu = pdrf[u];
-        if (!RAILS || fu != 0.0f) {
-          const float du = ld_f32_l2(&dist[u]);
-          if (du != KH_INF && du + fx == dx) {
-            strict = du < dx;
-            equal = (du == dx) && !(qstate[u] & 0x10);
-          }
-        }
-      }
-      if (head > 0 && __ballot(strict)) { found = head; break; }
-      const unsigned long long em = __ballot(equal);
-      const uint32_t cnt = (uint32_t)__popcll(em);
-      if (tail + cnt > bcap) { found = 0xFFFFFFFFu; head = tail; break; }
-      if (equal) {
-        const uint32_t p = tail + (uint32_t)__popcll(em & below);
-        bq[p] = u;
-        bpar[p] = head;
-        qstate[u] |= 0x10;
-      }
-      tail += cnt;
-      head++;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    }
-    for (uint32_t i = lane; i < tail; i += 64) qstate[bq[i]] &= (uint8_t)~0x10;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    if (found == 0xFFFFFFFFu) { if (lane == 0) atomicOr(status, KH_ST_PLATEAU); return 0; }
-    // route v -> ... -> bq[found] (the BFS tree, backwards), appended forwards
-    uint32_t len = 0;
-    for (uint32_t i = found; i != 0; i = bpar[i]) len++;
-    if (n + len > cap) { if (lane == 0) atomicOr(status, KH_ST_PATH_OVERFLOW); return 0; }
-    if (lane == 0) {
-      uint32_t pos = n + len - 1;
-      for (uint32_t i = found; i != 0; i = bpar[i]) out[pos--] = bq[i];
-    }
-    n += len;
-    v = bq[found];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  }
-  return n;
-}
-
-// everything the order-free sweep needs besides the per-label task record
-struct SweepGlobal {
-  uint32_t on;                  // 0 = sweep disabled (every invalidation runs as the heap emulation)
-  uint32_t gq, gx, gy, gz;      // integer mode (sweep.h): key^2 = gq * (gx a^2 + gy b^2 + gz c^2); gq == 0: table mode
-  const uint32_t* rank;         // table mode: level table [ra * rb * rc]
-  int ra, rb, rc;
-  unsigned long long* cstate;   // one word per voxel, all zero on entry and on exit
-  uint32_t* sched;              // one word per voxel (sweep.h, pending-deadline filter), SW_SCHED_NONE for live voxels; nullable
-  unsigned char* arena;         // event arenas (per label: kh_label_t.ev_offset, in units of 256 bytes)
-  uint32_t lds_levels;          // labels with more levels keep their level words in the arena instead of LDS
-  uint32_t heap_prio;           // != 0: the wave that runs the heap emulation raises its issue priority (s_setprio 3)
-};
-
-// Scratch on demand (round 6).  The heap of the exact emulation (16 B x 1.5 nodes per voxel) and the ghosts' journal (8 B per voxel)
-// were reserved for every label of a launch; 141 of c3's 3 402 labels ever run the emulation and 360 ever hold a ghost -- 4.6 GB per
-// volume in flight for 0.4 GB of use, and the volumes in flight are bounded by memory.  With KH_TRACE_SCRATCH_POOL `heap_nodes` is
-// ONE pool for the launch: node 0 = {nodes handed out so far (starts at 1), nodes in the pool}; a label takes what it needs when it
-// first needs it (one atomic add by one thread).  A label the pool cannot serve ends with KH_ST_HEAP_OVERFLOW (heap) -- the host
-// traces it again with scratch of its own, like every other overflow -- or goes on without ghosts (journal).
-// Whole workgroup; returns nullptr when the pool is exhausted.
-__device__ __forceinline__ hnode_t* pool_take(hnode_t* pool, uint32_t nodes, Ctl* ctl) {
-  if (threadIdx.x == 0) {
-    uint32_t* hdr = reinterpret_cast<uint32_t*>(pool);
-    const uint32_t cap = hdr[1];
-    uint32_t base = 0u;
-    if (nodes != 0u && nodes < cap) {
-      base = atomicAdd(&hdr[0], nodes);
-      if (base + nodes > cap || base + nodes < base) base = 0u;
-    }
-    ctl->pool_base = base;
-  }
-  __syncthreads();
-  const uint32_t b = ctl->pool_base;
-  __syncthreads();
-  return b ? pool + b : nullptr;
-}
-
-// One invalidation call by the whole workgroup: the order-free sweep when the label has a level table and the sweep
-// certifies the call, the heap emulation (wave 0) otherwise.  Returns the number of voxels invalidated (ghosts that were killed
-// not counted: sw->sh->nkg; ghosts made: sw->sh->nghost -- both zero unless allow_ghosts).
-//   kill_log      where the sweep logs the voxels it kills (+ the ghosts it makes): the label's journal in ghost mode
-//   allow_ghosts  a call that leaves voxels undecided ends as certified, the voxels become ghosts (sweep.h)
-//   force_heap    skip the sweep (the redo of a call after a roll-back)
-//   heap_ok       false while ghosts exist: the heap emulation needs the exact mask, so a call the sweep abandons cannot be
-//                 redone here -- ctl->u0 = 1 tells the caller to roll back (nothing has been changed)
-template <bool PROF, class H>
-__device__ __forceinline__ uint32_t invalidate(Ctl* ctl, Sweep* sw, kh_label_t* task, const uint32_t* __restrict__ nbrmask,
-                                               const float* __restrict__ dbf, uint8_t* alive, const uint32_t* path, uint32_t npath,
-                                               float scale, float constant, H& heap, const uint32_t* list, uint32_t nf,
-                                               uint32_t* sweep_stats, uint32_t heap_prio, uint32_t* kill_log,
-                                               bool allow_ghosts = false, bool force_heap = false, bool heap_ok = true,
-                                               const uint8_t* __restrict__ corner_gate = nullptr, hnode_t* pool = nullptr) {
-  const int tid = threadIdx.x;
-  bool ok = false;
-  if (tid == 0) {
-    sw->killed = (KH_AS_GLOBAL uint32_t*)kill_log;
-    sw->sh->nkg = 0u; sw->sh->nghost = 0u;
-    ctl->u0 = 0u;
-  }
-  __syncthreads();
-  if (!force_heap && sw->nlev != 0u && npath > 0 && npath <= 32766u && npath <= nf) {
-    const long long got = sweep_ball(*(const KH_AS_LDS Sweep*)sw, path, npath, dbf, scale, constant, task->sweep_rmax, list, nf, allow_ghosts);
-    ok = got >= 0;
-    const uint32_t cnt = ok ? (uint32_t)got : 0u;
-    if (tid == 0) {
-      sweep_stats[0]++;
-      sweep_stats[2] += sw->sh->levels;
-      sweep_stats[3] += sw->sh->events;
-#ifdef KH_SWEEP_PROBE
-      if (blockIdx.x == 0 || blockIdx.x == 100 || blockIdx.x == 1000 || blockIdx.x == 2500)
-        printf("SWCYC blk=%u nf=%u ok=%d lev=%u ev=%u commit=%llu next=%llu A=%llu cascA=%llu B=%llu cascB=%llu pairs=%llu "
-               "dn=%llu d_own=%llu d_alive=%llu d_rank=%llu d_sched=%llu d_casc=%llu d_push=%llu\n", blockIdx.x, nf, (int)ok,
-               sw->sh->levels, sw->sh->events, sw->sh->cyc[0], sw->sh->cyc[1], sw->sh->cyc[2], sw->sh->cyc[3], sw->sh->cyc[6],
-               sw->sh->cyc[4], sw->sh->cyc[5], sw->sh->cyd[7], sw->sh->cyd[0], sw->sh->cyd[1], sw->sh->cyd[2], sw->sh->cyd[3],
-               sw->sh->cyd[4], sw->sh->cyd[5]);
-#endif
-      if (!ok) { sweep_stats[1]++; sweep_stats[4] |= sw->sh->bail; sw->sh->nkg = 0u; sw->sh->nghost = 0u; }
-      if (sw->sh->maxnev > task->cyc_pop) task->cyc_pop = sw->sh->maxnev;   // diagnostic: busiest level
-      if (sw->sh->bump > task->cyc_push) task->cyc_push = sw->sh->bump;      // diagnostic: arena blocks used
-      ctl->u1 = cnt;
-    }
-  } else if (tid == 0 && force_heap) {
-    sweep_stats[1]++; sweep_stats[4] |= SW_BAIL_M;       // a call redone by the heap emulation after a roll-back
-  }
-  if (!ok && !heap_ok) {
-    if (tid == 0) { ctl->u0 = 1u; ctl->u1 = 0u; }
+// The second half of dijkstra3d.railroad (trace.py:240-242), by the whole workgroup right after sssp<1> from `src`: the walk back
+// from the nearest rail (out[0] = the rail end; wave 0, its length in ctl.u0, 0 on failure), then dist = +inf and the queue flags
+// cleared again on everything the search touched.  Returns ctl.u0 as it stands after the walk.  LOOP: the path loop's form --
+// ctl.u0 starts at 0 here and the voxels the search touched are added to ctl.u2 (kh_label_t.stat_settled).
+// (The sssp<1> call itself stays with the callers: made from in here, the copy of `q` it passes takes another stack slot.)
+template <bool LOOP>
+__device__ __forceinline__ uint32_t rail_walk(Ctl& ctl, const uint32_t* __restrict__ nbrmask, const float* pdrf, float* dist,
+                                              uint8_t* qstate, uint32_t src, const Queues& q, uint32_t* out, uint32_t cap, bool graph,
+                                              int nthr) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long br = ctl.best_rail;
+  if (LOOP) {
+    if (tid == 0) { ctl.u0 = 0; ctl.u2 += ctl.n_touched; }
     __syncthreads();
-    return 0u;
   }
-  if (!ok && heap.node == nullptr) {
-    // the label's first call of the heap emulation: its heap comes out of the launch's pool now
-    heap.node = pool != nullptr ? pool_take(pool, heap.cap, ctl) : nullptr;
-    if (heap.node == nullptr) {
-      if (tid == 0) { ctl->status |= KH_ST_HEAP_OVERFLOW; ctl->u1 = 0u; }
-      __syncthreads();
-      return 0u;
-    }
-  }
-  if (!ok) {
-    __syncthreads();
-    if (tid < 64) {
-      // The heap emulation is ONE sequential chain (a third of its time is instruction issue, the rest its own dependent
-      // loads) and it sets the wall clock of the label; the waves it shares its SIMD with -- other labels' sweeps and
-      // searches -- are throughput work.  With several volumes in flight they compete for issue slots all the time.
-      if (heap_prio) __builtin_amdgcn_s_setprio(3);
-      const uint32_t c = invalidate_ball<PROF, H>(ctl->g, task, nbrmask, dbf, alive, path, npath, scale, constant, heap,
-                                                  &ctl->status, &ctl->u3, ctl->cyc3, corner_gate);
-      if (heap_prio) __builtin_amdgcn_s_setprio(0);
-      if (tid == 0) ctl->u1 = c;
-    }
-    // the sweep reads "dead" from the filter words: bring them in line with the mask the heap emulation has edited (a pass over the
-    // label's voxels by the whole workgroup, once per such call -- a store per kill inside the emulation would sit on its chain)
-    if (sw->sched != nullptr && sw->nlev != 0u) {
-      __syncthreads();
-      sweep_reset_words(*(const KH_AS_LDS Sweep*)sw, list, nf);
-    }
+  if (br == NONE64) {
+    if (tid == 0) atomicOr(&ctl.status, KH_ST_NO_RAIL);
+  } else if (wave == 0) {
+    const uint32_t n = backtrack<true>(ctl.g, nbrmask, pdrf, dist, (uint32_t)br, src, out, cap, q.a, q.b, q.cap, qstate, &ctl.status, graph);
+    if (lane == 0) ctl.u0 = n;
   }
   __syncthreads();
-  const uint32_t c = ctl->u1;
-  __syncthreads();
-  return c;
-}
-
-// thread 0: fill the workgroup's Sweep record for `task` (LDS carve-out `lds` = the dynamic shared memory).  The kernel's
-// pointers get their address spaces here (sweep.h works on typed pointers only).
-__device__ __forceinline__ void sweep_setup(Sweep& sw, SweepShared* swsh, Ctl* ctl, const SweepGlobal& sg, const kh_label_t* task,
-                                            const uint32_t* nbrmask, uint8_t* alive, const Queues& q, uint32_t* killed,
-                                            uint32_t nf, unsigned char* lds, const uint8_t* corner_gate = nullptr) {
-  typedef KH_AS_GLOBAL unsigned char gbyte_t;
-  uint32_t nlev = (sg.on && sg.sched != nullptr) ? task->nlev : 0u;
-  sw.g = (const KH_AS_LDS Geometry*)&ctl->g;
-  sw.nbrmask = (const KH_AS_GLOBAL uint32_t*)nbrmask;
-  sw.alive = (KH_AS_GLOBAL uint8_t*)alive;
-  sw.cstate = (KH_AS_GLOBAL unsigned long long*)sg.cstate;
-  sw.sched = (KH_AS_GLOBAL uint32_t*)sg.sched;
-  sw.gq = sg.gq; sw.gx = sg.gx; sw.gy = sg.gy; sw.gz = sg.gz;
-  sw.rank = (const KH_AS_GLOBAL uint32_t*)sg.rank;
-  sw.ra = sg.ra; sw.rb = sg.rb;
-  // The searches' work lists (four of q.cap >= nf + 64 words) are free while an invalidation runs: the first is the kill log, the
-  // fourth (`touched`) holds the source records, the two between them the three lists of the level being processed (20 bytes per
-  // entry of each; a list that runs over abandons the call, SW_BAIL_LIST; so do more path vertices than records fit).  Round 5 kept
-  // all of this in the label's heap slice, which since round 6 only exists once the label needs the heap emulation.
-  {
-    const uintptr_t t0 = ((uintptr_t)q.touched + 15u) & ~(uintptr_t)15u;
-    sw.srcs = (KH_AS_GLOBAL u32x4_t*)(gbyte_t*)t0;
-    sw.srcs_cap = (uint32_t)(((uintptr_t)(q.touched + q.cap) - t0) / 16u);
-    const uintptr_t b0 = ((uintptr_t)q.b + 7u) & ~(uintptr_t)7u;
-    sw.ncap = (uint32_t)(((uintptr_t)(q.b + 2u * (size_t)q.cap) - b0) / 20u);
-    sw.wa = (KH_AS_GLOBAL unsigned long long*)(gbyte_t*)b0;
-    sw.np = sw.wa + sw.ncap;
-    sw.wb = (KH_AS_GLOBAL uint32_t*)(sw.np + sw.ncap);
+  const uint32_t plen = ctl.u0;
+  // restore dist = +inf and the queue flags on everything the search touched
+  const uint32_t nt = ctl.n_touched < q.cap ? ctl.n_touched : q.cap;
+  for (uint32_t i = tid; i < nt; i += nthr) {
+    const uint32_t v = q.touched[i];
+    st_f32_l2(&dist[v], KH_INF);
+    qstate[v] = 0;
   }
-  // level words + non-empty bitmap live in LDS: a window of them (kh_label_t.lev_window), or one per level when that fits the
-  // launch's allotment; a label for which neither does runs without the sweep (heap emulation only)
-  const uint32_t win = task->lev_window;
-  const bool windowed = win >= 64u && (win & (win - 1u)) == 0u && win <= sg.lds_levels;   // round-robin words
-  if (!windowed && nlev > sg.lds_levels) nlev = 0u;
-  sw.nslots = windowed ? win : nlev;
-  sw.wmask = windowed ? win - 1u : 0xFFFFFFFFu;
-  // arena: [spill table: ev_spill candidate words (u64) + ev_spill keys (u32)][(free stack of rounds 4-5: unused)][chunks]
-  gbyte_t* fsp = (gbyte_t*)(sg.arena + (size_t)task->ev_offset * 256u);
-  const uint32_t spcap = task->ev_spill;          // 0 or a power of two
-  sw.spcap = (spcap & (spcap - 1u)) == 0u ? spcap : 0u;
-  sw.spc = (KH_AS_GLOBAL unsigned long long*)fsp;
-  sw.spk = (KH_AS_GLOBAL uint32_t*)(fsp + (size_t)sw.spcap * 8u);
-  fsp += (((size_t)sw.spcap * 12u) + 255u) & ~(size_t)255u;
-  sw.chunks = (KH_AS_GLOBAL u32x2_t*)(fsp + ((((size_t)task->ev_chunks * 4u) + 255u) & ~(size_t)255u));
-  sw.chcap = task->ev_chunks;
-  sw.shift = (int)task->ev_shift;
-  sw.killed = (KH_AS_GLOBAL uint32_t*)killed;              // the search work lists are free during an invalidation
-  sw.nlev = nlev;                                          // 0: this label's invalidations run as the heap emulation
-  sw.chain = (KH_AS_LDS uint32_t*)lds;
-  sw.fs = sw.chain + SW_CHAIN;
-  sw.words = sw.fs + SW_RING;
-  sw.lvbits = sw.words + sw.nslots;
-  sw.sh = (KH_AS_LDS SweepShared*)swsh;
-  sw.gate = (const KH_AS_GLOBAL uint8_t*)corner_gate;
-  sw.xmin = task->xmin; sw.xmax = task->xmax;
+  return plen;
 }
-
-// Ghosts and roll-back.  A call of the sweep that leaves voxels undecided no longer runs the heap emulation
-// at once: the voxels become ghosts (sweep.h) and the loop goes on -- everything the later calls decide holds under either status
-// of a ghost, and most ghosts are killed for certain by a later ball.  The loop itself must never act on a ghost: when a ghost
-// could be the next target, when no certainly-valid voxel is left while ghosts are, or when a later call would need the heap
-// emulation (which needs the exact mask), the label ROLLS BACK to the call that made the first ghost -- the journal holds every
-// voxel that changed since (killed or made a ghost: all alive again), the rails of the later paths get their weights back -- and
-// that call is redone by the exact heap emulation; then the loop continues from there, without ghosts.
-struct GhostState {
-  uint32_t nghost;       // ghosts alive now
-  uint32_t jpos;         // journal entries (0 whenever no ghost exists)
-  uint32_t paths, verts, valid, nb, na;   // the state before the call that made the first ghost
-};
 
 template <bool PROF, int TOPL>
 #ifndef KH_TRACE_WAVES_PER_EU
@@ -1263,12 +127,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   const uint32_t* list = lists + task->list_offset;
   float* ldaf = list_daf + task->list_offset;
   const uint32_t nf = task->count;
-  Queues q;
-  q.cap = task->q_capacity;
-  q.a = queues + (uint64_t)task->q_offset * 4;
-  q.b = q.a + q.cap;
-  q.c = q.b + q.cap;
-  q.touched = q.c + q.cap;
+  const Queues q = task_queues(task, queues);
   Heap<TOPL> heap;
   hnode_t* const pool = (ghost_mode & 8u) ? heap_nodes : nullptr;      // KH_TRACE_SCRATCH_POOL: heap and journal on demand
   heap.node = pool ? nullptr : heap_nodes + task->heap_offset;
@@ -1361,7 +220,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
   if (nb + na >= max_paths) {                           // trace.py:217-218
     if (tid == 0) {
       task->n_paths = 0; task->n_vertices = 0; task->status |= ctl.status;
-      task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+      search_stats(task, ctl);
     }
     return;
   }
@@ -1434,25 +293,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
         plen = 1;
       } else {
         sssp<1>(ctl.g, nbrmask, pdrf, dist, qstate, target, q, &ctl, 0.0f, heap_top, lds_bytes);
-        const unsigned long long br = ctl.best_rail;
-        if (tid == 0) { ctl.u0 = 0; ctl.u2 += ctl.n_touched; }
-        __syncthreads();
-        if (br == NONE64) {
-          if (tid == 0) atomicOr(&ctl.status, KH_ST_NO_RAIL);
-        } else if (wave == 0) {
-          const uint32_t n = backtrack<true>(ctl.g, nbrmask, pdrf, dist, (uint32_t)br, target, out, pcap - nverts, q.a, q.b,
-                                             q.cap, qstate, &ctl.status, graph);
-          if (lane == 0) ctl.u0 = n;
-        }
-        __syncthreads();
-        plen = ctl.u0;
-        // restore dist = +inf and the queue flags on everything the search touched
-        const uint32_t nt = ctl.n_touched < q.cap ? ctl.n_touched : q.cap;
-        for (uint32_t i = tid; i < nt; i += nthr) {
-          const uint32_t v = q.touched[i];
-          st_f32_l2(&dist[v], KH_INF);
-          qstate[v] = 0;
-        }
+        plen = rail_walk<true>(ctl, nbrmask, pdrf, dist, qstate, target, q, out, pcap - nverts, graph, nthr);
         __syncthreads();
         if (plen == 0) break;
       }
@@ -1583,7 +424,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
     task->n_paths = npaths;
     task->n_vertices = nverts;
     task->status |= ctl.status;
-    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+    search_stats(task, ctl);
     task->stat_settled = ctl.u2;
     task->stat_heap_pushes = ctl.u3;
     task->cyc_target = (uint32_t)(t_target >> 10);
@@ -1592,11 +433,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void trace_paths_kernel
     if (PROF) task->cyc_pop = (uint32_t)(ctl.cyc3[0] >> 10);
     if (PROF) task->cyc_push = (uint32_t)(ctl.cyc3[1] >> 10);
     task->cyc_fire = (uint32_t)(ctl.cyc3[2] >> 10);
-    task->stat_sweep_calls = sweep_stats[0];
-    task->stat_sweep_bails = sweep_stats[1];
-    task->stat_sweep_levels = sweep_stats[2];
-    task->stat_sweep_events = sweep_stats[3];
-    task->stat_sweep_why = sweep_stats[4];
+    sweep_stats_store(task, sweep_stats);
     task->stat_ghost_calls = n_ghost_calls;
     task->stat_rollbacks = n_rollbacks;
   }
@@ -1629,12 +466,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void invalidate_ball_ke
   if (tid == 0) {
     ctl.status = 0; ctl.u1 = 0; ctl.u3 = 0; ctl.cyc3[0] = ctl.cyc3[1] = ctl.cyc3[2] = 0; ctl.g = g;
     for (int i = 0; i < 5; i++) sweep_stats[i] = 0;
-    Queues q;
-    q.cap = task->q_capacity;
-    q.a = queues + (uint64_t)task->q_offset * 4;
-    q.b = q.a + q.cap;
-    q.c = q.b + q.cap;
-    q.touched = q.c + q.cap;
+    const Queues q = task_queues(task, queues);
     sweep_setup(sw, &swsh, &ctl, sg, task, nbrmask, alive, q, q.a, nf, heap_top, corner_gate);
   }
   __syncthreads();
@@ -1649,11 +481,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void invalidate_ball_ke
     *invalidated = (long long)c;
     task->status |= ctl.status;
     task->stat_heap_pushes = ctl.u3;
-    task->stat_sweep_calls = sweep_stats[0];
-    task->stat_sweep_bails = sweep_stats[1];
-    task->stat_sweep_levels = sweep_stats[2];
-    task->stat_sweep_events = sweep_stats[3];
-    task->stat_sweep_why = sweep_stats[4];
+    sweep_stats_store(task, sweep_stats);
   }
 }
 
@@ -1670,12 +498,7 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void path_search_kernel
   __shared__ Ctl ctl;
   __shared__ __attribute__((aligned(16))) unsigned char search_lds[KH_SSSP_LDS_BYTES * 256];
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
-  Queues q;
-  q.cap = task->q_capacity;
-  q.a = queues + (uint64_t)task->q_offset * 4;
-  q.b = q.a + q.cap;
-  q.c = q.b + q.cap;
-  q.touched = q.c + q.cap;
+  const Queues q = task_queues(task, queues);
   if (tid == 0) { ctl.status = 0; ctl.u0 = 0; ctl.n_retries = ctl.n_spills = ctl.n_splits = 0; ctl.g = g; }
   __syncthreads();
   if (mode == 1) {
@@ -1690,21 +513,12 @@ __global__ __launch_bounds__(256, KH_TRACE_WAVES_PER_EU) void path_search_kernel
     if (tid == 0) { out[0] = src; ctl.u0 = 1; }
   } else {
     sssp<1>(ctl.g, nbrmask, pdrf, dist, qstate, src, q, &ctl, 0.0f, search_lds, (uint32_t)sizeof(search_lds));
-    const unsigned long long br = ctl.best_rail;
-    if (br == NONE64) {
-      if (tid == 0) atomicOr(&ctl.status, KH_ST_NO_RAIL);
-    } else if (wave == 0) {
-      const uint32_t n = backtrack<true>(ctl.g, nbrmask, pdrf, dist, (uint32_t)br, src, out, cap, q.a, q.b, q.cap, qstate, &ctl.status, graph != 0);
-      if (lane == 0) ctl.u0 = n;
-    }
-    __syncthreads();
-    const uint32_t nt = ctl.n_touched < q.cap ? ctl.n_touched : q.cap;
-    for (uint32_t i = tid; i < nt; i += nthr) { const uint32_t v = q.touched[i]; st_f32_l2(&dist[v], KH_INF); qstate[v] = 0; }
+    rail_walk<false>(ctl, nbrmask, pdrf, dist, qstate, src, q, out, cap, graph != 0, nthr);
   }
   __syncthreads();
   if (tid == 0) {
     *out_n = ctl.u0; task->status |= ctl.status;
-    task->stat_search_retries += ctl.n_retries; task->stat_search_spills += ctl.n_spills; task->stat_search_splits += ctl.n_splits;
+    search_stats(task, ctl);
   }
 }
 
@@ -1894,29 +708,45 @@ static bool sweep_global(SweepGlobal& sg, const uint32_t* level_rank, int64_t ra
   sg.on = 1u;
   return true;
 }
-template <bool PROF, int TOPL = 1>
-static int launch_trace(int count, hipStream_t st, kh_label_t* tasks, const uint32_t* lists, float* list_daf,
-                        const uint32_t* nbrmask, const Geometry& g, const float* dbf, float* pdrf, float* dist,
-                        uint8_t* alive, uint8_t* qstate, const uint32_t* manual_targets, float scale, float constant,
-                        uint32_t* queues, hnode_t* heap_nodes, uint32_t* path_vertices, uint32_t* path_lengths,
-                        int fix_branching, const SweepGlobal& sg, uint32_t max_nlev, unsigned nthreads, uint32_t* journal,
-                        float* rail_save, uint32_t ghost_mode, const uint8_t* corner_gate) {
-  if (count <= 0) return KH_OK;
-  size_t lds = Heap<TOPL>::LDS_BYTES;          // the heap's LDS part (and key mirror)
+static int sweep_args_error(const char* entry) {
+  set_error("%s: sweep arguments (level table or integer-mode factors, cstate, sched, a 256-byte aligned event arena, max_nlev)", entry);
+  return KH_EINVAL;
+}
+// Dynamic LDS of a launch of `kernel` whose workgroups run the heap emulation, the sweep and -- search_threads != 0 -- the searches
+// in the same bytes: the largest of the heap's LDS part with its key mirror (heap_bytes), the sweep's words for max_nlev levels
+// when the sweep is on, and the searches' scratch.  Allows the kernel that much as well.
+static int trace_lds_bytes(const void* kernel, size_t heap_bytes, const SweepGlobal& sg, uint32_t max_nlev, unsigned search_threads,
+                           size_t& lds) {
+  lds = heap_bytes;
   const size_t swl = sweep_lds_bytes(max_nlev);
   if (sg.on && swl > lds) lds = swl;
-  if ((size_t)KH_SSSP_LDS_BYTES * nthreads > lds) lds = (size_t)KH_SSSP_LDS_BYTES * nthreads;     // the searches' scratch (same bytes)
-  {
-    // More than 48 KiB of dynamic LDS has to be allowed per kernel.  The attribute belongs to the function, not to the
-    // launch, and several host threads launch at once (kimimaro_amd/lanes.py): always the same value -- the largest a
-    // launch can ask for -- so that a concurrent caller never lowers it under somebody else's launch.
-    const size_t lds_max = sweep_lds_bytes(KH_SWEEP_LDS_LEVELS);
-    KH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&trace_paths_kernel<PROF, TOPL>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_max > lds ? lds_max : lds)));
-  }
-  hipLaunchKernelGGL((trace_paths_kernel<PROF, TOPL>), dim3(count), dim3(nthreads), lds, st, tasks, lists, list_daf, nbrmask,
-                     g, dbf, pdrf, dist, alive, qstate, manual_targets, scale, constant, queues, heap_nodes, path_vertices,
-                     path_lengths, fix_branching, sg, journal, rail_save, ghost_mode, corner_gate, (uint32_t)lds);
+  if ((size_t)KH_SSSP_LDS_BYTES * search_threads > lds) lds = (size_t)KH_SSSP_LDS_BYTES * search_threads;
+  // More than 48 KiB of dynamic LDS has to be allowed per kernel.  The attribute belongs to the function, not to the
+  // launch, and several host threads launch at once (kimimaro_amd/lanes.py): always the same value -- the largest a
+  // launch can ask for -- so that a concurrent caller never lowers it under somebody else's launch.
+  const size_t lds_max = sweep_lds_bytes(KH_SWEEP_LDS_LEVELS);
+  KH_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_max > lds ? lds_max : lds)));
+  return KH_OK;
+}
+// what trace_paths_kernel takes (in its order), and the launch's shape
+struct TraceArgs {
+  int count; unsigned nthreads; uint32_t max_nlev; hipStream_t st;
+  kh_label_t* tasks; const uint32_t* lists; float* list_daf; const uint32_t* nbrmask; Geometry g; const float* dbf;
+  float *pdrf, *dist; uint8_t *alive, *qstate; const uint32_t* manual_targets; float scale, constant; uint32_t* queues;
+  hnode_t* heap_nodes; uint32_t *path_vertices, *path_lengths; int fix_branching; SweepGlobal sg; uint32_t* journal;
+  float* rail_save; uint32_t ghost_mode; const uint8_t* corner_gate;
+};
+template <bool PROF, int TOPL = 1>
+static int launch_trace(const TraceArgs& a) {
+  if (a.count <= 0) return KH_OK;
+  size_t lds;
+  if (int rc = trace_lds_bytes(reinterpret_cast<const void*>(&trace_paths_kernel<PROF, TOPL>), Heap<TOPL>::LDS_BYTES, a.sg, a.max_nlev,
+                               a.nthreads, lds))
+    return rc;
+  hipLaunchKernelGGL((trace_paths_kernel<PROF, TOPL>), dim3(a.count), dim3(a.nthreads), lds, a.st, a.tasks, a.lists, a.list_daf,
+                     a.nbrmask, a.g, a.dbf, a.pdrf, a.dist, a.alive, a.qstate, a.manual_targets, a.scale, a.constant, a.queues,
+                     a.heap_nodes, a.path_vertices, a.path_lengths, a.fix_branching, a.sg, a.journal, a.rail_save, a.ghost_mode,
+                     a.corner_gate, (uint32_t)lds);
   KH_LAUNCH_CHECK();
   return KH_OK;
 }
@@ -1970,27 +800,18 @@ extern "C" int kh_trace_paths(kh_label_t* tasks, int ntasks, const uint32_t* lis
   Geometry g;
   make_geometry(g, sx, sy, sz, wx, wy, wz);
   SweepGlobal sg;
-  if (!sweep_global(sg, level_rank, ra, rb, rc, wx, wy, wz, cstate, sched, event_arena, max_nlev)) {
-    set_error("kh_trace_paths: sweep arguments (level table or integer-mode factors, cstate, sched, a 256-byte aligned event arena, max_nlev)");
-    return KH_EINVAL;
-  }
+  if (!sweep_global(sg, level_rank, ra, rb, rc, wx, wy, wz, cstate, sched, event_arena, max_nlev)) return sweep_args_error("kh_trace_paths");
   sg.heap_prio = (flags & KH_TRACE_HEAP_PRIO) ? 1u : 0u;
-  hipStream_t st = (hipStream_t)stream;
-  const bool prof = (flags & KH_TRACE_PROFILE) != 0;
   // ghosts need the journal (and, with rails, the saved weights); bit 1: roll every ghost call back at once
   const bool use_pool = (flags & KH_TRACE_SCRATCH_POOL) != 0;
   const uint32_t ghost_mode = ((journal || use_pool) && !(flags & KH_TRACE_NO_GHOSTS) ? 1u : 0u) | ((flags & KH_TRACE_GHOST_PARANOID) ? 2u : 0u) |
                               ((flags & KH_TRACE_VOXEL_GRAPH) ? 4u : 0u) | (use_pool ? 8u : 0u) | ((flags & KH_TRACE_FUSED_EDF) ? 16u : 0u);
-  if (flags & KH_TRACE_BIG_LDS_HEAP)
-    return launch_trace<false, 2>(ntasks, st, tasks, lists, list_daf, nbrmask, g, dbf, pdrf, dist, alive, qstate, manual_targets,
-                                  scale, constant, queues, (hnode_t*)heap_nodes, path_vertices, path_lengths, fix_branching, sg,
-                                  (uint32_t)max_nlev, nthreads, journal, rail_save, ghost_mode, corner_gate);
-  return prof ? launch_trace<true>(ntasks, st, tasks, lists, list_daf, nbrmask, g, dbf, pdrf, dist, alive, qstate, manual_targets,
-                                   scale, constant, queues, (hnode_t*)heap_nodes, path_vertices, path_lengths, fix_branching, sg,
-                                   (uint32_t)max_nlev, nthreads, journal, rail_save, ghost_mode, corner_gate)
-              : launch_trace<false>(ntasks, st, tasks, lists, list_daf, nbrmask, g, dbf, pdrf, dist, alive, qstate, manual_targets,
-                                    scale, constant, queues, (hnode_t*)heap_nodes, path_vertices, path_lengths, fix_branching, sg,
-                                    (uint32_t)max_nlev, nthreads, journal, rail_save, ghost_mode, corner_gate);
+  const TraceArgs a = {ntasks, nthreads, (uint32_t)max_nlev, (hipStream_t)stream, tasks, lists, list_daf, nbrmask, g, dbf, pdrf, dist,
+                       alive, qstate, manual_targets, scale, constant, queues, (hnode_t*)heap_nodes, path_vertices, path_lengths,
+                       fix_branching, sg, journal, rail_save, ghost_mode, corner_gate};
+  if (flags & KH_TRACE_BIG_LDS_HEAP) return launch_trace<false, 2>(a);
+  if (flags & KH_TRACE_PROFILE) return launch_trace<true>(a);
+  return launch_trace<false>(a);
 }
 
 extern "C" int kh_invalidate_ball(kh_label_t* task, const uint32_t* lists, const uint32_t* nbrmask, int64_t sx, int64_t sy,
@@ -2008,19 +829,10 @@ extern "C" int kh_invalidate_ball(kh_label_t* task, const uint32_t* lists, const
   Geometry g;
   make_geometry(g, sx, sy, sz, wx, wy, wz);
   SweepGlobal sg;
-  if (!sweep_global(sg, level_rank, ra, rb, rc, wx, wy, wz, cstate, sched, event_arena, max_nlev)) {
-    set_error("kh_invalidate_ball: sweep arguments (level table or integer-mode factors, cstate, sched, a 256-byte aligned event arena, max_nlev)");
-    return KH_EINVAL;
-  }
-  size_t lds = Heap<1>::LDS_BYTES;
-  const size_t swl = sweep_lds_bytes((uint32_t)max_nlev);
-  if (sg.on && swl > lds) lds = swl;
-  {
-    // (constant value: see launch_trace)
-    const size_t lds_max = sweep_lds_bytes(KH_SWEEP_LDS_LEVELS);
-    KH_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&invalidate_ball_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_max > lds ? lds_max : lds)));
-  }
+  if (!sweep_global(sg, level_rank, ra, rb, rc, wx, wy, wz, cstate, sched, event_arena, max_nlev)) return sweep_args_error("kh_invalidate_ball");
+  size_t lds;
+  if (int rc2 = trace_lds_bytes(reinterpret_cast<const void*>(&invalidate_ball_kernel), Heap<1>::LDS_BYTES, sg, (uint32_t)max_nlev, 0u, lds))
+    return rc2;
   hipLaunchKernelGGL(invalidate_ball_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, task, lists, nbrmask, g, dbf, alive, queues,
                      (hnode_t*)heap_nodes, path, (uint32_t)npath, scale, constant, sg, (long long*)invalidated, corner_gate);
   KH_LAUNCH_CHECK();

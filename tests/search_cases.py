@@ -1,4 +1,4 @@
-"""The inputs of the search-regime tests: small, deterministic, each built for one part of sssp (csrc/trace.hip).
+"""The inputs of the search-regime tests: small, deterministic, each built for one part of sssp (csrc/sssp.h).
 tests/test_search_ref_host.py proves search_ref == oracle on every one of them without a GPU; tests/test_gpu_search_regimes.py
 runs them on the device.  Masks and fields are built on demand (`case["mask"]()`); points are (x, y, z)."""
 import numpy as np

@@ -1,7 +1,7 @@
-"""A reference for the searches of csrc/trace.hip that shares nothing with them or with the oracle's heap Dijkstra: the Bellman
+"""A reference for the searches of csrc/sssp.h that shares nothing with them or with the oracle's heap Dijkstra: the Bellman
 fixpoint d[v] = min over allowed neighbours u of fl32(d[u] + w), computed by 26 shifted-array relaxations in numpy float32,
 repeated until no word changes.  No heap, no work lists, no order: distances start at +inf (0 at the source) and only go down, and
-fl32(d + w) is monotone in d, so the iteration ends at the fixpoint the header comment of trace.hip claims.
+fl32(d + w) is monotone in d, so the iteration ends at the fixpoint the header comment of csrc/trace.hip claims.
 
 Volumes are (x, y, z), Fortran order, linear index = x + sx * (y + sy * z).  A graph (cc3d's layout, voxel_graphs.GRAPH_BIT) gates a
 step by the word of the voxel being EXPANDED (u), so an asymmetric graph gives one-way edges."""

@@ -1,4 +1,4 @@
-"""The heap emulation's key mirror (csrc/trace.hip: heap levels 7-10 as LDS keys, one global round trip per pop for heaps
+"""The heap emulation's key mirror (csrc/heap.h: heap levels 7-10 as LDS keys, one global round trip per pop for heaps
 below 131 072 nodes) against the oracle's restatement of the reference's heap, at every heap size at which a pop takes
 another way down: the LDS part alone (< 127 nodes), the mirror stage alone (< 2 047), one global chunk under a mirrored hole
 (what used to be one chunk below 8 191 nodes and two above it).  sweep = False: every call is the heap emulation.

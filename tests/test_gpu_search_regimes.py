@@ -1,4 +1,4 @@
-"""The searches of csrc/trace.hip (sssp<MODE>) on their own, in the regimes the whole-product tests do not show they reach: the
+"""The searches of csrc/sssp.h (sssp<MODE>) on their own, in the regimes the whole-product tests do not show they reach: the
 combine table full (an offer finds no slot, the frontier voxel is relaxed again), the near lists beyond their LDS part, hundreds
 of far-list splits, and the rows27 loads at the first and last word of the array.  Inputs come from tests/search_cases.py; every
 case first asserts, from the kernels' own counters (kh_label_t.stat_search_*), that it was in the regime it is built for, then

@@ -58,7 +58,7 @@ def check_result(case, cnt, after):
 def sweep_runs(eng, task):
     """does the object of this record get the sweep at all?  Its level words live in LDS: a window of them, or all of them; an object
     whose balls have more levels than that (a large radius under a coarse anisotropy) runs on the heap emulation only, by design
-    (trace.hip, sweep_setup: "a label for which neither does runs without the sweep"; plan.plan_sweep says the same)."""
+    (invalidate.h, sweep_setup: "a label for which neither does runs without the sweep"; plan.plan_sweep says the same)."""
     nlev, win = int(task["nlev"][0]), int(task["lev_window"][0])
     windowed = win >= 64 and win & (win - 1) == 0 and win <= eng.sweep_lds_levels
     return nlev > 0 and (windowed or nlev <= eng.sweep_lds_levels)
@@ -133,7 +133,7 @@ def test_many_owners(engines, mode):
 
 def spill_table(eng, ctx):
     """the bytes of the context's spill table: the front of its arena, ev_spill candidate words of 8 bytes, then ev_spill keys of 4
-    (trace.hip, sweep_setup: sw.spc, sw.spk)"""
+    (invalidate.h, sweep_setup: sw.spc, sw.spk)"""
     n = int(ctx["task"]["ev_spill"][0]) * 12
     off = int(ctx["arena_ptr"].value) - int(ctx["d_arena"].data_ptr())
     assert n > 0 and int(ctx["task"]["ev_offset"][0]) == 0

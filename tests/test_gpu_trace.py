@@ -291,7 +291,7 @@ def test_skeletonize_fuzz_small_volumes(eng, seed):
 @pytest.mark.parametrize("sweep,slots", [(False, 3), (False, 128), (True, 3), (True, 128)])
 def test_skeletonize_sweep_and_heap_paths(sweep, slots):
     """The invalidation has two implementations: the order-free level sweep (csrc/sweep.h) and the exact emulation
-    of the reference's heap (the sweep's fall-back).  Both must give the oracle's skeletons; the volume is one
+    of the reference's heap (csrc/heap.h, the sweep's fall-back).  Both must give the oracle's skeletons; the volume is one
     whose heaps outgrow the LDS part.  `slots` forces the two-stream split of the labels (3 of 7, and all)."""
     import kimimaro_amd
     from kimimaro_amd.engine import Engine

@@ -1,4 +1,4 @@
-"""SWCYC lines of a -DKH_SWEEP_PROBE build (csrc/trace.hip) -> cycles per level and per deadline event, by label."""
+"""SWCYC lines of a -DKH_SWEEP_PROBE build (printed by csrc/invalidate.h, counted in csrc/sweep.h) -> cycles per level and per deadline event, by label."""
 import collections
 import re
 import sys
