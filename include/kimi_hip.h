@@ -434,7 +434,12 @@ int kh_fill_voids_nd(const uint8_t* mask, int ndim, int64_t sx, int64_t sy, int6
  *   a cut, low[p] the neighbour of high[p]; the distinct keys low[p] << 32 | high[p] are put into `table` with kh_region_pairs'
  *   layout, capacity rule, `state` and overflow report (call again with a larger table).  The caller numbers the regions so that
  *   low[p] < high[p]; no labels are read: whether a pair joins two pieces of one region (equal value) or two adjacent regions is
- *   the caller's to tell.                                                                                                        */
+ *   the caller's to tell.
+ * kh_region_apply_box: kh_region_apply for a core of a dataset.  region (u32 [nvox]) holds the DATASET's
+ *   provisional ids; the core owns base + 1 .. base + nregions (nregions >= 1, base + nregions <= 2^32 - 1) and owner (u64
+ *   [nregions + 1], entry 0 unused) is the table of those.  Per voxel r = region[v] - base in u32 arithmetic: for r in 1..nregions
+ *   labels[v] = owner[r] where that is non-zero; for any other r the voxel is left alone and owner is NOT read.  state (device u64
+ *   [2], set by the call): [0] = voxels painted, [1] = voxels whose id lay outside the core's range (a stale region store).        */
 int kh_regions6(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, uint32_t* parent, uint32_t* chunk_counts,
                 uint32_t* region, uint32_t* representative, uint32_t* nregions, void* stream);
 int kh_region_table(const void* labels, int label_bytes, const uint32_t* region, const uint32_t* representative, int64_t nregions,
@@ -447,6 +452,8 @@ int kh_region_table_box(const void* labels, int label_bytes, const uint32_t* reg
                         uint8_t* face, void* stream);
 int kh_region_seam_pairs(const uint32_t* low, const uint32_t* high, int64_t m, uint64_t* table, int64_t capacity, uint32_t* state,
                          void* stream);
+int kh_region_apply_box(const uint32_t* region, uint32_t base, int64_t nregions, const uint64_t* owner, void* labels, int label_bytes,
+                        int64_t nvox, uint64_t* state, void* stream);
 /* host (no GPU needed): who fills what, on the region graph.  value / count / face: the table of kh_region_table ([nregions + 1]);
  * pairs: u64 [npairs], the non-empty keys of kh_region_pairs in any order, each unordered pair once.  The labels (non-zero values,
  * compared as unsigned words) are gone through in ascending order with a dead set, as the reference's loop does:

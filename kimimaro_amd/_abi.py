@@ -26,7 +26,7 @@ SYMBOLS = [
     "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
     "kh_cross_sections_box", "kh_cross_sections_fixed_exponent", "kh_cross_sections_filled_box",
     "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
-    "kh_region_table_box", "kh_region_seam_pairs",
+    "kh_region_table_box", "kh_region_seam_pairs", "kh_region_apply_box",
     "kh_part_gaps", "kh_host_join_plan",
 ]
 
@@ -190,6 +190,7 @@ def lib():
     L.kh_region_apply.argtypes = [vp, vp, vp, ci, i64, vp]
     L.kh_region_table_box.argtypes = [vp, ci, vp, vp, i64, ci, i64, i64, i64, C.c_uint32, vp, vp, vp, vp]
     L.kh_region_seam_pairs.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    L.kh_region_apply_box.argtypes = [vp, C.c_uint32, i64, vp, vp, ci, i64, vp, vp]
     L.kh_host_resolve_holes.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.kh_host_resolve_holes.restype = i64
     L.kh_host_enclosed_regions.argtypes = [i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]

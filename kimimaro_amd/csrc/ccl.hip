@@ -660,6 +660,31 @@ __global__ __launch_bounds__(256) void reg_apply_kernel(const uint32_t* __restri
   }
 }
 
+// apply for a core of a dataset: the ids are the dataset's provisional ids, the table holds the core's own range
+// base + 1 .. base + nregions.  An id outside that range reads no table entry: the voxel is left alone and counted in state[1] (the
+// ids may come from a caller's file).  One block-uniform trip count, so every ballot sees its whole wave; a wave sums its two
+// counts over its trips and adds each with one atomic at the end.
+template <typename LT>
+__global__ __launch_bounds__(256) void reg_apply_box_kernel(const uint32_t* __restrict__ region, uint32_t base, uint32_t nregions,
+                                                            const unsigned long long* __restrict__ owner, LT* __restrict__ lab, int64_t n,
+                                                            unsigned long long* state) {
+  unsigned long long painted = 0ull, outside = 0ull;
+  for (int64_t t = (int64_t)blockIdx.x * 256; t < n; t += (int64_t)gridDim.x * 256) {
+    const int64_t i = t + threadIdx.x;
+    const bool valid = i < n;
+    const uint32_t r = valid ? region[i] - base : 1u;                     // u32 arithmetic: an id below base wraps above nregions
+    const bool known = r - 1u < nregions;
+    const unsigned long long o = (valid && known) ? owner[r] : 0ull;
+    if (o != 0ull) lab[i] = (LT)o;
+    painted += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(o != 0ull));
+    outside += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(valid && !known));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (painted) atomicAdd(&state[0], painted);
+    if (outside) atomicAdd(&state[1], outside);
+  }
+}
+
 }  // namespace kh
 
 #define KH_REG_DISPATCH(bytes, name, CALL)                   \
@@ -773,6 +798,26 @@ extern "C" int kh_region_apply(const uint32_t* region, const uint64_t* owner, vo
   KH_REG_DISPATCH(label_bytes, "kh_region_apply",
                   hipLaunchKernelGGL((kh::reg_apply_kernel<LT>), dim3(kh::ccl_grid(nvox, 256)), dim3(256), 0, st, region,
                                      (const unsigned long long*)owner, (LT*)labels, nvox));
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_region_apply_box(const uint32_t* region, uint32_t base, int64_t nregions, const uint64_t* owner, void* labels,
+                                   int label_bytes, int64_t nvox, uint64_t* state, void* stream) {
+  if (int rc = kh::require_device()) return rc;
+  if (!region || !owner || !labels || !state || nvox <= 0 || nvox >= (1ll << 32) - 1 || nregions < 1 ||
+      (int64_t)base + nregions > (1ll << 32) - 1 || (label_bytes != 1 && label_bytes != 2 && label_bytes != 4 && label_bytes != 8)) {
+    kh::set_error("kh_region_apply_box: bad arguments (null pointer, empty volume or >= 2^32-1 voxels, nregions < 1, "
+                  "base + nregions above 2^32-1, or label_bytes not 1, 2, 4 or 8)");      // (before anything is written)
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  KH_HIP_CHECK(hipMemsetAsync(state, 0, 2 * sizeof(uint64_t), st));
+  // a streaming pass: blocks that stride over the volume, a few per CU, rather than one short-lived block per 256 voxels
+  KH_REG_DISPATCH(label_bytes, "kh_region_apply_box",
+                  hipLaunchKernelGGL((kh::reg_apply_box_kernel<LT>), dim3(kh::ccl_grid(nvox, 256, 2048)), dim3(256), 0, st, region, base,
+                                     (uint32_t)nregions, (const unsigned long long*)owner, (LT*)labels, nvox,
+                                     (unsigned long long*)state));
   KH_LAUNCH_CHECK();
   return KH_OK;
 }

@@ -372,6 +372,20 @@ class Engine:
             raise _abi.KimiHipError("kh_region_seam_pairs: %d keys counted, %d found in the table" % (int(state[0]), keys.size))
         return keys, cap, tries
 
+    def region_apply_box(self, d_region, base, d_owner, d_lab, label_bytes):
+        """kh_region_apply_box: paints a core of a dataset, resident in HBM, in place.  d_region: the core's slice of
+        the region store (u32 provisional ids, one per voxel of d_lab); d_owner: u64 [nregions + 1] on the device, the owners of the
+        ids base + 1 .. base + nregions (entry 0 unused).  -> (voxels painted, voxels whose id lay outside that range: they are left
+        alone and no table entry is read for them)."""
+        self.edited(d_lab)
+        n = int(d_region.numel())
+        assert int(d_lab.numel()) == n
+        d_state = self.empty(2, self.torch.int64)
+        _abi.check(self.lib.kh_region_apply_box(self.ptr(d_region), int(base), int(d_owner.numel()) - 1, self.ptr(d_owner), self.ptr(d_lab),
+                                                int(label_bytes), n, self.ptr(d_state), self.stream()))
+        state = d_state.cpu().numpy().view(np.uint64)
+        return int(state[0]), int(state[1])
+
     def fill_all_holes(self, d_lab, label_bytes, shape, ndim=3, stats=None):
         """kimimaro.intake.fill_all_holes (kimimaro/intake.py:747-795) on a label volume resident in HBM (1-D, Fortran order, 1 / 2 / 4 /
         8 bytes per label; modified in place): the holes of every label in ONE pass over the volume instead of a fill per bounding

@@ -11,7 +11,7 @@
 
 What else is done to a dataset in boxes lives one layer down and is imported here, so that every name stays reachable as
 kimimaro_amd.post.NAME: the sections (section_boxes: cross_sectional_area_chunked, cross_sectional_area_filled_chunked,
-region_graph_chunked, hole_lists, RegionGraph, XS_CLIPPED) and the segments (segment_boxes: oversegment_chunked, shell_diff, DIRECTIONS).
+region_graph_chunked, hole_lists, fill_all_holes_chunked, RegionGraph, XS_CLIPPED) and the segments (segment_boxes: oversegment_chunked, shell_diff, DIRECTIONS).
 
 Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
 functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
@@ -33,11 +33,11 @@ from collections import defaultdict
 import numpy as np
 
 from . import _abi, intake, ops, points
-from .boxes import _load_box, axes
+from .boxes import _load_box, axes, label_type
 from .lanes import Lanes, lanes_for
 from .plan import chunk_grid
 from .section_boxes import (XS_CLIPPED, RegionGraph, cross_sectional_area_chunked, cross_sectional_area_filled_chunked,  # noqa: F401
-                            hole_lists, region_graph_chunked)
+                            fill_all_holes_chunked, hole_lists, region_graph_chunked)
 from .segment_boxes import DIRECTIONS, oversegment_chunked, shell_diff  # noqa: F401
 from .skeleton import Skeleton
 
@@ -259,7 +259,8 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
                         dust_threshold=1000, dust_global=False, post_dust_threshold=1500.0, tick_threshold=3000.0, merge=True,
                         fix_branching=True, fix_borders=True, fill_holes=False, fix_avocados=False, extra_targets_before=[],
                         extra_targets_after=[], progress=False, lanes=None, width=None, timings=None, _skeletonize=None,
-                        _postprocess=None, cross_sectional_area=None):
+                        _postprocess=None, cross_sectional_area=None, fill_holes_global=False, filled_store=None, region_store=None,
+                        _fill=None):
     """A dataset in chunks to whole skeletons, {label: Skeleton} in ascending label order: what igneous does around
     kimimaro.skeletonize and kimimaro.postprocess, in one call.
 
@@ -283,9 +284,18 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
       every returned skeleton its sections (`anisotropy` defaults to this call's); ignored with merge=False.
     lanes, width: as in skeletonize_many -- a Lanes object to reuse, else `width` lanes are made (default: lanes_for() on the
       largest box), never more than there are chunks.
+    fill_holes_global: the holes of every label are filled on the DATASET first (fill_all_holes_chunked) and the
+      result is DEFINED as skeletonize_chunked of the filled dataset with fill_holes=False: a cavity that a cut runs through is
+      filled, what lay in it gets no skeleton.  fill_all_holes_chunked(dataset, chunk_shape, out=filled_store,
+      region_store=region_store, return_fill_count=True) runs in front of everything; the dataset is not modified.  The labels of
+      dust_global are counted on the filled store, every box is cut out of it and traced with fill_holes=False whatever
+      `fill_holes` says, and cross_sectional_area= takes its sections on it.
+    filled_store: where the filled dataset is kept, an array-like of the dataset's shape and dtype written and read by slices;
+      default: a numpy array in host memory.  region_store: fill_all_holes_chunked's (4 bytes per voxel of the dataset).
     progress: accepted, no effect.
     timings (a dict) receives count_s, chunks_s, place_s, fuse_s, post_s (seconds), chunks (boxes traced), fragments and vertices
-      (of the placed fragments).
+      (of the placed fragments); with fill_holes_global also fill_s and filled (the fill count).
+    _fill replaces fill_all_holes_chunked (the host-logic tests hand it their hooks).
     _skeletonize(labels, **kwargs) -> {label: Skeleton} runs the boxes one after the other in place of the lanes,
     _postprocess(skeletons, dust_threshold, tick_threshold) -> list replaces postprocess_many: with both, nothing here touches the GPU
       (the host-logic tests run the whole driver on the CPU oracle).  Without them there is no CPU fallback."""
@@ -302,6 +312,16 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
     before = route_targets(extra_targets_before, grid, shape)
     after = route_targets(extra_targets_after, grid, shape)
     wanted = None if object_ids is None else set(int(v) for v in object_ids)
+
+    fill_s, filled = 0.0, 0
+    if fill_holes_global:
+        t0 = time.perf_counter()
+        if filled_store is None:
+            filled_store = np.empty(shape, dtype=label_type(dataset)[0], order="F")
+        dataset, filled = (fill_all_holes_chunked if _fill is None else _fill)(dataset, chunk_shape, out=filled_store,
+                                                                              region_store=region_store, return_fill_count=True)
+        fill_holes = False
+        fill_s = time.perf_counter() - t0
 
     t0 = time.perf_counter()
     kept = None
@@ -356,6 +376,8 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
         timings.update(count_s=count_s, chunks_s=chunks_s, place_s=place_s, fuse_s=0.0, post_s=0.0,
                        chunks=sum(res is not None for res in results), fragments=sum(len(f) for f in fragments.values()),
                        vertices=sum(s.vertices.shape[0] for f in fragments.values() for s in f))
+        if fill_holes_global:
+            timings.update(fill_s=fill_s, filled=int(filled))
     if not merge:
         return fragments
 
