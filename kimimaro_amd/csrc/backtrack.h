@@ -10,9 +10,10 @@ namespace kh {
 //   - normally pred(v) = the achieving neighbour (fl(d[u] + f[v]) == d[v]) with d[u] < d[v] minimising (d[u], index);
 //   - at the rail end of a railroad (f == 0) every achieving neighbour has d[u] == d[v]: smallest index;
 //   - float-absorption plateau (all achieving neighbours have d[u] == d[v]): breadth-first search over the
-//     equal-distance achieving neighbours (FIFO, neighbours in direction order) to the first voxel with a
-//     strictly smaller achieving predecessor; the BFS route is followed.  bq / bpar: scratch lists (>= Nf
-//     entries), visited marks live in bit 4 of the label's own qstate bytes.
+//     equal-distance achieving neighbours (FIFO, neighbours in direction order) to the first voxel that is
+//     `target` (the search's source: zero weights around it make a plateau at distance 0 that nothing lies
+//     below) or has a strictly smaller achieving predecessor; the BFS route is followed.  bq / bpar: scratch
+//     lists (>= Nf entries), visited marks live in bit 4 of the label's own qstate bytes.
 // With a voxel graph (kh_apply_voxel_graph) the masks are one-way: bit k of nbrmask[v] says "a step FROM v in direction k is
 // allowed".  A predecessor u of v needs the step u -> v, i.e. the bit of the OPPOSITE direction in u's word; without a graph
 // the masks are symmetric and v's own word serves (one load less per step).
@@ -96,7 +97,7 @@ __device__ __attribute__((noinline)) uint32_t backtrack(const Geometry& g, const
           }
         }
       }
-      if (head > 0 && __ballot(strict)) { found = head; break; }
+      if (head > 0 && (x == target || __ballot(strict))) { found = head; break; }
       const unsigned long long em = __ballot(equal);
       const uint32_t cnt = (uint32_t)__popcll(em);
       if (tail + cnt > bcap) { found = 0xFFFFFFFFu; head = tail; break; }

@@ -405,7 +405,8 @@ static int ko_field_sssp(const float* f, int64_t sx, int64_t sy, int64_t sz, uin
  *   - at the rail end of a railroad (f == 0): every achieving neighbour has d[u] == d[v]; take the smallest index;
  *   - float-absorption plateau (a step cost below half an ulp of the accumulated distance: every achieving
  *     neighbour has d[u] == d[v]): breadth-first search over the equal-distance achieving neighbours
- *     (FIFO, neighbours in direction order 0..25) to the first voxel that has a strictly smaller achieving
+ *     (FIFO, neighbours in direction order 0..25) to the first voxel that is `stop` (zero weights around the
+ *     source make a plateau at distance 0 that nothing lies below) or has a strictly smaller achieving
  *     predecessor; the BFS route is followed.  A real Dijkstra resolves such plateaus by its heap order. */
 static int ko_pred_strict(const float* f, const float* d, int64_t sx, int64_t sy, int64_t sz,
                           uint64_t v, int rails_absorb, int allow_equal, uint64_t* pred) {
@@ -458,7 +459,7 @@ static int ko_walk(const float* f, const float* d, int64_t sx, int64_t sy, int64
     while (head < tail) {
       const uint64_t x = q[head];
       uint64_t tmp;
-      if (head > 0 && ko_pred_strict(f, d, sx, sy, sz, x, rails_absorb, 0, &tmp)) { found = head; break; }
+      if (head > 0 && (x == stop || ko_pred_strict(f, d, sx, sy, sz, x, rails_absorb, 0, &tmp))) { found = head; break; }
       int64_t xz = (int64_t)(x / (uint64_t)sxy), xr = (int64_t)(x % (uint64_t)sxy), xy = xr / sx, xx = xr % sx;
       for (int i = 0; i < 26; i++) {
         int64_t nx = xx + KO_DIR[i][0], ny = xy + KO_DIR[i][1], nz = xz + KO_DIR[i][2];
