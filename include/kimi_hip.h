@@ -295,6 +295,26 @@ int kh_invalidate_ball(kh_label_t* task, const uint32_t* lists, const uint32_t* 
                        uint64_t* cstate, uint32_t* sched, void* event_arena, const uint8_t* corner_gate, int64_t* invalidated,
                        void* stream);
 
+/* ---- the invalidation heap on its own (csrc/heap.h: the wave-cooperative emulation of std::priority_queue with
+ * Compare = `a.dist >= b.dist`), driven by a script.  For tests; the product does not call it.  One workgroup of one wave builds
+ * the heap exactly as kh_trace_paths does (topl 1: 127 slots in LDS and the key mirror of slots 127..2046; topl 2, the heap of
+ * KH_TRACE_BIG_LDS_HEAP: 8191 slots in LDS, no mirror; cap = min(capacity, what a pop can descend through)) and walks `ops`.
+ *   ops     device array of nops records of four uint32 words {op, a, b, c}:
+ *             {0, key bits, payload, source}  push: a push at n >= cap is refused and counted in state[1]
+ *             {1, -, -, -}                    pop: appends {key bits, payload, source, n before the pop} of the top to `pops`, then
+ *                                             removes it.  On an empty heap: counted in state[2], skipped.
+ *             {2, flags, -, -}                dump: appends to `dumps` the header {n, index of this record}, then the n nodes in slot
+ *                                             order (four words each: key bits, payload, source, the unused word), then -- topl 1 --
+ *                                             the mirror's key words of slots 127 .. min(n, 2047)-1.  flags bit 0: the header only.
+ *           Any other op is counted in state[2] and skipped.  Keys are the bit patterns of non-negative floats below +inf.
+ *   nodes   device array of nodes_allocated 16-byte nodes, 16-byte aligned: the heap's slots in memory (slots below 127 / 8191 live
+ *           in LDS and are never written here).  nodes_allocated >= max(capacity, 128 / 8192): a clamped load reads slot 127 / 8191.
+ *   pops, dumps   device arrays of pops_capacity / dumps_capacity uint32 WORDS.  A pop record or a dump that does not fit is not
+ *           written (the pop itself still happens) and counted in state[3].
+ *   state   four device words, written at the end: {n, refused pushes, script errors, records that did not fit}.        */
+int kh_heap_script(int topl, const uint32_t* ops, int64_t nops, void* nodes, int64_t nodes_allocated, uint32_t capacity,
+                   uint32_t* pops, int64_t pops_capacity, uint32_t* dumps, int64_t dumps_capacity, uint32_t* state, void* stream);
+
 /* ---- a7 / a8 on their own: one search on one object (the path loop has them inside kh_trace_paths).
  * field: the weight volume (PDRF; +inf outside the object); dist: f32 volume, +inf on entry; qstate / queues as for
  * kh_edf_batch; task: the object's kh_label_t (q_offset / q_capacity, count).
