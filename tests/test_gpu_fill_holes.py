@@ -212,15 +212,12 @@ def test_pair_table_overflow_is_retried(eng):
         assert stats[key] >= 0
 
 
-@pytest.mark.parametrize("shape,dtype", [((70, 33, 21), np.uint16), ((130, 9, 5), np.uint64), ((5, 6, 7), np.uint8)])
-def test_region_graph_against_numpy(eng, shape, dtype):
-    """the device's regions, table and pairs equal numpy's up to the numbering of the regions; the device numbers them by first
-    appearance in the raster"""
-    rng = np.random.default_rng(shape[0])
-    cc = np.asfortranarray(rng.integers(0, 3, shape).astype(dtype) * dtype(41))
-    cc[2:-1, 2:-1, 2:-1] = np.where(rng.random(cc[2:-1, 2:-1, 2:-1].shape) < 0.6, dtype(7), cc[2:-1, 2:-1, 2:-1])
-    value, count, face, pairs, region = fill_ref.region_graph(cc)
-    d_region, g_value, g_count, g_face, g_pairs, info = eng.region_graph(eng.to_device(cc), cc.dtype.itemsize, cc.shape)
+def assert_region_graph(eng, cc, ndim=3):
+    """the device's regions, table and pairs of `cc` (three axes; ndim < 3: the trailing ones have extent 1 and are no axes) equal
+    numpy's up to the numbering of the regions; the device numbers them by first appearance in the raster"""
+    value, count, face, pairs, region = fill_ref.region_graph(cc.reshape(cc.shape[:ndim]))
+    region = region.reshape(cc.shape)
+    d_region, g_value, g_count, g_face, g_pairs, info = eng.region_graph(eng.to_device(cc), cc.dtype.itemsize, cc.shape, ndim)
     got = eng.to_host_volume(d_region, cc.shape).astype(np.int64)
     nreg = len(value) - 1
     assert info["regions"] == nreg and got.min() == 1 and got.max() == nreg
@@ -237,6 +234,15 @@ def test_region_graph_against_numpy(eng, shape, dtype):
     mapped = (np.minimum(lo, hi).astype(np.uint64) << np.uint64(32)) | np.maximum(lo, hi).astype(np.uint64)
     assert len(np.unique(g_pairs)) == len(g_pairs)
     assert np.array_equal(np.sort(mapped), pairs)
+    return nreg
+
+
+@pytest.mark.parametrize("shape,dtype", [((70, 33, 21), np.uint16), ((130, 9, 5), np.uint64), ((5, 6, 7), np.uint8)])
+def test_region_graph_against_numpy(eng, shape, dtype):
+    rng = np.random.default_rng(shape[0])
+    cc = np.asfortranarray(rng.integers(0, 3, shape).astype(dtype) * dtype(41))
+    cc[2:-1, 2:-1, 2:-1] = np.where(rng.random(cc[2:-1, 2:-1, 2:-1].shape) < 0.6, dtype(7), cc[2:-1, 2:-1, 2:-1])
+    assert_region_graph(eng, cc)
 
 
 @pytest.mark.parametrize("dtype,scale", [(np.uint8, 1), (np.uint16, 1000), (np.uint32, 1), (np.uint32, (1 << 31) + 5), (np.uint64, (1 << 40) + 3),

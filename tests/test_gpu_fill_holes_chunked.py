@@ -62,7 +62,7 @@ def painted_by_numpy(region, base, nregions, owner, labels):
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.uint64])
-@pytest.mark.parametrize("nvox", [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4099])
+@pytest.mark.parametrize("nvox", [1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4099, 524_288, 524_289, 2 * 524_288 + 77])
 def test_apply_box_against_numpy(eng, nvox, dtype):
     rng = np.random.default_rng(nvox)
     for base in (0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1 - NREG):
@@ -90,12 +90,11 @@ def test_apply_box_paints_owners_above_2_63(eng):
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint64])
 @pytest.mark.parametrize("base", [0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1 - NREG - PAD])
-def test_apply_box_leaves_ids_outside_the_range_alone(eng, base, dtype):
+def test_apply_box_leaves_ids_outside_the_range_alone(eng, base, dtype, nvox=2000):
     """The owner buffer is longer than the table and holds non-zero sentinels in entry 0 and behind entry NREG; the ids outside the
     range are `base` itself and base + NREG + 1 .. base + NREG + PAD.  Without the guard such a voxel would be painted with a
     sentinel read inside the allocation; no id below `base` is used."""
     rng = np.random.default_rng(3)
-    nvox = 2000
     owner = owners(rng, dtype, NREG, extra=PAD)
     owner[0] = 0x55
     owner[NREG + 1:] = 0x66
@@ -110,6 +109,13 @@ def test_apply_box_leaves_ids_outside_the_range_alone(eng, base, dtype):
     assert n_outside == int(stray.sum()) >= 500 and n_painted > 300
     assert np.array_equal(got[stray], labels[stray])                       # no sentinel was painted
     assert np.array_equal(got, want) and state.tolist() == [n_painted, n_outside]
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint64])
+@pytest.mark.parametrize("base", [0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 32 - 1 - NREG - PAD])
+def test_apply_box_leaves_ids_outside_the_range_alone_on_later_trips(eng, base, dtype):
+    """the same with more voxels than two trips of the capped grid cover (2048 blocks of 256)"""
+    test_apply_box_leaves_ids_outside_the_range_alone(eng, base, dtype, nvox=2 * 524_288 + 77)
 
 
 def test_apply_box_bad_arguments(eng):
