@@ -567,6 +567,22 @@ int kh_nearest_label_voxels(const void* labels, int label_bytes, int64_t sx, int
                             const uint64_t* table, const uint32_t* query_start, int64_t nlabels, const double* centroids,
                             int64_t nqueries, uint64_t* best_distance, uint64_t* best_voxel, void* stream);
 
+/* ---- the same for a dataset that is never resident as a whole: ONE visit of ONE box, on running per-query results that live on
+ * the device across visits (csrc/points.hip).  labels: the box, [ex,ey,ez] Fortran ordered, its low corner at
+ * (lox, loy, loz) of a dataset whose y and z extents are dsy, dsz.  table / query_start / centroids as above, for the nqueries queries
+ * of THIS visit, centroids in dataset coordinates; query_index: u32 [nqueries], the row g of each listed query in the running
+ * arrays best_distance / best_voxel (distinct rows), which the caller sets to ~0 once and which are never filled here.  On return,
+ * for every listed query, (best_distance[g], best_voxel[g]) is the lexicographic minimum of the pair that came in and, over the
+ * box's voxels of the query's label, (bits of d, C-order index in the DATASET ((lox+x)*dsy + (loy+y))*dsz + (loz+z), 64 bit), d as
+ * above from dx = (double)(lox + x) - cx and likewise y, z.  A box that lowers best_distance[g] thereby discards the best_voxel[g]
+ * earlier boxes found; with an equal distance the earlier index stays and competes.  Rows not listed are not touched.
+ * scratch: u64 [nqueries].  Everything is stream-ordered, no host synchronisation, nothing is allocated.                          */
+int kh_nearest_label_voxels_box(const void* labels, int label_bytes, int64_t ex, int64_t ey, int64_t ez,
+                                int64_t lox, int64_t loy, int64_t loz, int64_t dsy, int64_t dsz,
+                                const uint64_t* table, const uint32_t* query_start, int64_t nlabels, const double* centroids,
+                                const uint32_t* query_index, int64_t nqueries, uint64_t* best_distance, uint64_t* best_voxel,
+                                uint64_t* scratch, void* stream);
+
 /* ---- skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086 -> skeletontricks.hpp:399-495) on the words of
  * kh_neighbor_mask of the image (foreground = one label): every unordered pair of foreground voxels that are neighbours in one of
  * `directions` (bit i = direction i of that mask: 0x3F connectivity 6, 0x3FFFF 18, 0x3FFFFFF 26) is an edge, every voxel on an edge a

@@ -22,7 +22,7 @@ SYMBOLS = [
     "kh_host_consolidate_paths",
     "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
     "kh_geodesic_seed_at", "kh_box_shell_diff", "kh_first_appearance_box",
-    "kh_nearest_label_voxels", "kh_binary_edge_count", "kh_binary_edge_emit",
+    "kh_nearest_label_voxels", "kh_nearest_label_voxels_box", "kh_binary_edge_count", "kh_binary_edge_emit",
     "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
     "kh_cross_sections_box", "kh_cross_sections_fixed_exponent", "kh_cross_sections_filled_box",
     "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
@@ -172,6 +172,7 @@ def lib():
     L.kh_box_shell_diff.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
     L.kh_first_appearance_box.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp]
     L.kh_nearest_label_voxels.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp]
+    L.kh_nearest_label_voxels_box.argtypes = [vp, ci, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
     L.kh_binary_edge_count.argtypes = [vp, i64, C.c_uint32, vp, vp, vp, vp]
     L.kh_binary_edge_emit.argtypes = [vp, i64, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]
     f64 = C.c_double

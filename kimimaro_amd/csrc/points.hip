@@ -4,6 +4,10 @@
 //                             of that label nearest to the centroid -- scipy's cdist + np.argmin(axis=0) over
 //                             np.vstack((labels == label).nonzero()).T, for ALL labels and centroids in two passes over the volume
 //                             instead of one pass and one dense distance matrix per label.
+//   kh_nearest_label_voxels_box   the same two passes on ONE BOX of a dataset that is never resident as a whole, on running per-query
+//                             results that stay on the device from box to box (synapses_to_targets_chunked):
+//                             distances from dataset coordinates, the dataset's C-order index, and the carry rule -- a box that
+//                             lowers a query's distance discards the index earlier boxes found for it.
 //   kh_binary_edge_count /    skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086, skeletontricks.hpp:399-495)
 //   kh_binary_edge_emit       on the words of kh_neighbor_mask: count, (the caller's scan), emit -- in a canonical order instead of
 //                             the iteration order of an unordered_set.
@@ -93,6 +97,90 @@ __global__ __launch_bounds__(256) void nearest_kernel(const LT* __restrict__ lab
           const unsigned long long c = ((unsigned long long)x * (unsigned long long)sy + (unsigned long long)y) * (unsigned long long)sz + (unsigned long long)z;
           const unsigned long long m = wave_min_u64(hit ? c : ~0ull);
           if (hit && c == m && m < best_c[q]) atomicMin(&best_c[q], m);
+        }
+      }
+    }
+  }
+}
+
+// ONE BOX of a dataset that is never resident as a whole: the two passes of nearest_kernel on a box of extent
+// (ex, ey, ez) whose low corner lies at (lox, loy, loz) of a dataset with y and z extents dsy, dsz.  Distances are taken from the
+// DATASET coordinates of a voxel, the index is the dataset's C-order index, and the results are RUNNING ones: query q of this visit
+// owns row qidx[q] of best_d / best_c, which come in holding the best of the boxes visited so far and are never filled here.
+//   carry_save   scratch[q] = best_d[qidx[q]]                        the distances that came in
+//   PASS 1       best_d[g] = min(itself, the box's distances)        as nearest_kernel
+//   carry_reset  best_c[g] = ~0 where best_d[g] != scratch[q]         a lowered distance makes the index of earlier boxes stale
+//   PASS 2       best_c[g] = min(itself, the box's indices at best_d[g])   an index that was kept competes with this box's
+__global__ void carry_save_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
+                                  unsigned long long* __restrict__ scratch) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) scratch[q] = best_d[qidx[q]];
+}
+
+__global__ void carry_reset_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
+                                   const unsigned long long* __restrict__ scratch, unsigned long long* __restrict__ best_c) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = qidx[q];
+    if (best_d[g] != scratch[q]) best_c[g] = ~0ull;
+  }
+}
+
+template <typename LT, int PASS>
+__global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__ lab, int ex, int ey, int ez, int64_t lox, int64_t loy,
+                                                          int64_t loz, int64_t dsy, int64_t dsz, int64_t tiles_per_block,
+                                                          const unsigned long long* __restrict__ table,
+                                                          const uint32_t* __restrict__ qstart, int nlab, const double* __restrict__ cen,
+                                                          const uint32_t* __restrict__ qidx, unsigned long long* best_d,
+                                                          unsigned long long* best_c) {
+  const int xt = (ex + 255) >> 8;
+  const int64_t ntiles = (int64_t)xt * ey * ez;
+  const int64_t t0 = (int64_t)blockIdx.x * tiles_per_block;
+  const int64_t t1 = (t0 + tiles_per_block < ntiles) ? t0 + tiles_per_block : ntiles;
+  unsigned long long lastL = 0;
+  int lastSlot = -2;                      // -2: nothing looked up yet; -1: lastL is not in the table
+  for (int64_t t = t0; t < t1; t++) {
+    const int x = (int)(t % xt) * 256 + (int)threadIdx.x;
+    const int64_t r = t / xt;
+    const int y = (int)(r % ey), z = (int)(r / ey);
+    int slot = -1;
+    if (x < ex) {
+      const unsigned long long L = (unsigned long long)lab[x + (int64_t)ex * (y + (int64_t)ey * z)];
+      if (lastSlot == -2 || L != lastL) {
+        int lo = 0, hi = nlab;            // first entry >= L
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (table[mid] < L) lo = mid + 1; else hi = mid;
+        }
+        lastL = L;
+        lastSlot = (lo < nlab && table[lo] == L) ? lo : -1;
+      }
+      slot = lastSlot;
+    }
+    const int64_t X = lox + x, Y = loy + y, Z = loz + z;       // the voxel in the dataset
+    unsigned long long todo = __ballot(slot >= 0);
+    while (todo) {
+      const int s = __shfl(slot, __ffsll((long long)todo) - 1);
+      const bool mine = slot == s;
+      todo &= ~__ballot(mine);
+      const uint32_t q0 = qstart[s], q1 = qstart[s + 1];
+      for (uint32_t q = q0; q < q1; q++) {
+        const uint32_t g = qidx[q];
+        const double dx = (double)X - cen[3 * (size_t)q + 0];
+        const double dy = (double)Y - cen[3 * (size_t)q + 1];
+        const double dz = (double)Z - cen[3 * (size_t)q + 2];
+        const double d = __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+        const unsigned long long key = (unsigned long long)__double_as_longlong(d);
+        const unsigned long long cur = best_d[g];     // PASS 1: may be stale, i.e. too large -- costs an atomic, never a result
+        if (PASS == 1) {
+          if (!__any(mine && key < cur)) continue;
+          const unsigned long long m = wave_min_u64(mine ? key : ~0ull);
+          const unsigned long long holders = __ballot(mine && key == m);
+          if ((int)(threadIdx.x & 63) == __ffsll((long long)holders) - 1) atomicMin(&best_d[g], m);
+        } else {
+          const bool hit = mine && key == cur;
+          if (!__any(hit)) continue;
+          const unsigned long long c = ((unsigned long long)X * (unsigned long long)dsy + (unsigned long long)Y) * (unsigned long long)dsz + (unsigned long long)Z;
+          const unsigned long long m = wave_min_u64(hit ? c : ~0ull);
+          if (hit && c == m && m < best_c[g]) atomicMin(&best_c[g], m);
         }
       }
     }
@@ -213,6 +301,43 @@ extern "C" int kh_nearest_label_voxels(const void* labels, int label_bytes, int6
                                                      (int)sy, (int)sz, per_block, (const unsigned long long*)table, query_start,
                                                      (int)nlabels, centroids, (unsigned long long*)best_distance,
                                                      (unsigned long long*)best_voxel));
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
+
+extern "C" int kh_nearest_label_voxels_box(const void* labels, int label_bytes, int64_t ex, int64_t ey, int64_t ez, int64_t lox,
+                                           int64_t loy, int64_t loz, int64_t dsy, int64_t dsz, const uint64_t* table,
+                                           const uint32_t* query_start, int64_t nlabels, const double* centroids,
+                                           const uint32_t* query_index, int64_t nqueries, uint64_t* best_distance,
+                                           uint64_t* best_voxel, uint64_t* scratch, void* stream) {
+  if (int rc = require_device()) return rc;
+  if (ex <= 0 || ey <= 0 || ez <= 0 || ex >= (1ll << 31) || ey >= (1ll << 31) || ez >= (1ll << 31) || lox < 0 || loy < 0 || loz < 0 ||
+      dsy <= 0 || dsz <= 0 || nlabels <= 0 || nlabels >= (1ll << 31) || nqueries <= 0 || nqueries >= (1ll << 32)) {
+    set_error("kh_nearest_label_voxels_box: extents in [1, 2^31), lo >= 0, dataset extents >= 1, 1 <= nlabels < 2^31, "
+              "1 <= nqueries < 2^32");
+    return KH_EINVAL;
+  }
+  if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4 && label_bytes != 8) {
+    set_error("label_bytes must be 1, 2, 4 or 8");
+    return KH_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* bd = (unsigned long long*)best_distance;
+  unsigned long long* bc = (unsigned long long*)best_voxel;
+  const unsigned qgrid = points_grid((nqueries + 255) / 256, 1024);
+  const int64_t ntiles = ((ex + 255) / 256) * ey * ez;
+  const unsigned blocks = points_grid(ntiles, 4096);     // the sibling's launch shape, on the box
+  const int64_t per_block = (ntiles + blocks - 1) / blocks;
+  hipLaunchKernelGGL(carry_save_kernel, dim3(qgrid), dim3(256), 0, st, query_index, nqueries, bd, (unsigned long long*)scratch);
+  KH_POINTS_DISPATCH(label_bytes, hipLaunchKernelGGL((nearest_box_kernel<LT, 1>), dim3(blocks), dim3(256), 0, st, (const LT*)labels,
+                                                     (int)ex, (int)ey, (int)ez, lox, loy, loz, dsy, dsz, per_block,
+                                                     (const unsigned long long*)table, query_start, (int)nlabels, centroids,
+                                                     query_index, bd, bc));
+  hipLaunchKernelGGL(carry_reset_kernel, dim3(qgrid), dim3(256), 0, st, query_index, nqueries, bd, (unsigned long long*)scratch, bc);
+  KH_POINTS_DISPATCH(label_bytes, hipLaunchKernelGGL((nearest_box_kernel<LT, 2>), dim3(blocks), dim3(256), 0, st, (const LT*)labels,
+                                                     (int)ex, (int)ey, (int)ez, lox, loy, loz, dsy, dsz, per_block,
+                                                     (const unsigned long long*)table, query_start, (int)nlabels, centroids,
+                                                     query_index, bd, bc));
   KH_LAUNCH_CHECK();
   return KH_OK;
 }

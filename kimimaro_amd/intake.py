@@ -159,6 +159,51 @@ def _label_word(label, span, itemsize):
     return value % (1 << (8 * itemsize))
 
 
+def synapse_queries(synapses, span, itemsize):
+    """The queries of synapses_to_targets for a volume whose dtype holds `span` in `itemsize` bytes -> (groups, words, query_start,
+    centroids), None when no label is left.  groups: per entry of `synapses`, in its order, (word, {swc label: [centroids]}) with the
+    swc labels in first-seen order (intake.py:735-737), None for a label the dtype cannot hold, one without pairs and a repeated
+    word; words: u64, the distinct words ascending; query_start: u32 [len(words) + 1]; centroids: f64 [Q, 3], the queries of
+    words[k] at rows [query_start[k], query_start[k + 1]), swc label after swc label."""
+    groups, by_word = [], {}
+    for label, pairs in synapses.items():
+        word = _label_word(label, span, itemsize)
+        swc = {}
+        for centroid, swc_label in pairs:
+            swc.setdefault(swc_label, []).append(np.asarray(centroid, dtype=np.float64).reshape(3))
+        if word is None or not swc or word in by_word:
+            groups.append(None)
+            continue
+        by_word[word] = len(groups)
+        groups.append((word, swc))
+    if not by_word:
+        return None
+    words = np.array(sorted(by_word), dtype=np.uint64)
+    counts = [sum(len(c) for c in groups[by_word[int(w)]][1].values()) for w in words]
+    query_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint32)
+    centroids = np.concatenate([np.stack(c) for w in words for c in groups[by_word[int(w)]][1].values()])
+    return groups, words, query_start, centroids
+
+
+def synapse_targets(groups, words, query_start, winners, sy, sz):
+    """{(x, y, z): swc_label} from the winners (u64 [Q]: C-order indices x*sy*sz + y*sz + z, points.NONE64 where the label does not
+    occur) of the queries of synapse_queries, in the reference's insertion and overwrite order"""
+    targets = {}
+    for g in groups:
+        if g is None:
+            continue
+        word, swc = g
+        at = int(query_start[int(np.searchsorted(words, np.uint64(word)))])
+        for swc_label, cens in swc.items():
+            won = winners[at:at + len(cens)]
+            at += len(cens)
+            if won[0] == points.NONE64:              # the label does not occur (intake.py:732-733)
+                break
+            for c in np.unique(won).tolist():        # np.unique(np.argmin(...)): ascending C order
+                targets[(c // (sy * sz), (c // sz) % sy, c % sz)] = swc_label
+    return targets
+
+
 def synapses_to_targets(labels, synapses, progress=False):
     """kimimaro.synapses_to_targets (kimimaro/intake.py:706-745): turn the output of synapse detection into targets for
     skeletonize(extra_targets_after=...).  synapses: { label: [ (centroid, swc_label), ... ] }, centroid an (x, y, z) float triple in
@@ -180,42 +225,12 @@ def synapses_to_targets(labels, synapses, progress=False):
         raise DimensionError("synapses_to_targets needs a 3-D label volume. Got: {}".format(tuple(labels.shape)))
     eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     d_flat, itemsize, _, shape, _, span = _device_labels(eng, labels)
-    sx, sy, sz = shape
-
-    # per label that the dtype can hold: its swc labels in first-seen order, each with its centroids (intake.py:735-737)
-    groups, by_word = [], {}
-    for label, pairs in synapses.items():
-        word = _label_word(label, span, itemsize)
-        swc = {}
-        for centroid, swc_label in pairs:
-            swc.setdefault(swc_label, []).append(np.asarray(centroid, dtype=np.float64).reshape(3))
-        if word is None or not swc or word in by_word:
-            groups.append(None)
-            continue
-        by_word[word] = len(groups)
-        groups.append((word, swc))
-    if not by_word:
+    queries = synapse_queries(synapses, span, itemsize)
+    if queries is None:
         return {}
-    words = np.array(sorted(by_word), dtype=np.uint64)
-    counts = [sum(len(c) for c in groups[by_word[int(w)]][1].values()) for w in words]
-    query_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint32)
-    centroids = np.concatenate([np.stack(c) for w in words for c in groups[by_word[int(w)]][1].values()])
+    groups, words, query_start, centroids = queries
     winners = points.nearest_label_voxels(eng, d_flat, itemsize, shape, words, query_start, centroids)
-
-    targets = {}
-    for g in groups:
-        if g is None:
-            continue
-        word, swc = g
-        at = int(query_start[int(np.searchsorted(words, np.uint64(word)))])
-        for swc_label, cens in swc.items():
-            won = winners[at:at + len(cens)]
-            at += len(cens)
-            if won[0] == points.NONE64:              # the label does not occur (intake.py:732-733)
-                break
-            for c in np.unique(won).tolist():        # np.unique(np.argmin(...)): ascending C order
-                targets[(c // (sy * sz), (c // sz) % sy, c % sz)] = swc_label
-    return targets
+    return synapse_targets(groups, words, query_start, winners, shape[1], shape[2])
 
 
 def connect_points(labels, start, end, anisotropy=(1, 1, 1), fill_holes=False, in_place=False, pdrf_scale=100000, pdrf_exponent=4):

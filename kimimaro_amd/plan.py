@@ -423,3 +423,27 @@ def neighbor_cores(grid, steps):
     """int64 [chunks, len(steps)]: per chunk of the ChunkGrid `grid` the row of the chunk one step (dx, dy, dz) away in the grid, for each
     of `steps`; -1 where the grid ends"""
     return core_index(grid.grid, grid.grid_index[:, None, :] + np.asarray(steps, dtype=np.int64).reshape(1, -1, 3))
+
+
+# -- which cores a nearest-voxel query has to look at (synapses_to_targets_chunked, DESIGN.md 3.20) ------------------------------
+def box_distance_bounds(core_lo, core_hi, centroids):
+    """float64 [n_cores, Q]: the distance from each centroid (f64 [Q, 3], dataset coordinates) to the nearest voxel CENTRE a core
+    [core_lo, core_hi) could hold -- p = clip(c, lo, hi - 1), then kh_nearest_label_voxels_box's own expression
+    sqrt((dx*dx + dy*dy) + dz*dz) with d = p - c, every operation rounded in float64.  For a voxel v of the core, |v - c| >= |p - c|
+    per axis as reals (p is c itself or the end of the core's range on c's side), and subtraction, the square of a magnitude, the
+    sum of non-negative terms and the root are all monotone when rounded: the bound is <= the distance the kernel computes for
+    every voxel of the core AS FLOATS.  A query is skipped in a core only when bound > its best so far, strictly (an equal distance
+    still competes on the index), so a skipped core cannot have changed the result.  A label that occurs nowhere never gets a
+    best: its queries stay active in every core -- the whole-volume call, too, looks everywhere to learn that."""
+    lo = np.asarray(core_lo, dtype=np.float64).reshape(-1, 1, 3)
+    top = np.asarray(core_hi, dtype=np.float64).reshape(-1, 1, 3) - 1.0
+    c = np.asarray(centroids, dtype=np.float64).reshape(1, -1, 3)
+    dx, dy, dz = (np.clip(c[..., a], lo[..., a], top[..., a]) - c[..., a] for a in range(3))
+    return np.sqrt((dx * dx + dy * dy) + dz * dz)
+
+
+def nearest_first(bounds):
+    """the visit order of the cores: ascending by a core's smallest bound over all queries, ties in raster order (stable) -- the
+    cores that can hold a winner come first, which lets the rule above skip the others; the result does not depend on it"""
+    bounds = np.asarray(bounds, dtype=np.float64)
+    return np.argsort(bounds.min(axis=1) if bounds.shape[1] else np.zeros(bounds.shape[0]), kind="stable")

@@ -53,6 +53,39 @@ def nearest_label_voxels(eng, d_lab, label_bytes, shape, words, query_start, cen
     return d_vox.cpu().numpy().view(np.uint64)
 
 
+def nearest_label_voxels_box(eng, d_lab, label_bytes, extent, lo, dataset_shape, words, query_start, centroids, query_index, d_best,
+                             d_vox):
+    """One visit of one box of a dataset (kh_nearest_label_voxels_box).  d_lab: the box on the device (1-D, Fortran
+    order) of `extent` voxels with its low corner at `lo` of a dataset of `dataset_shape`; words / query_start / centroids as in
+    nearest_label_voxels for the queries of THIS visit, centroids in dataset coordinates; query_index: u32 [Q], the row of each of
+    them in the running arrays d_best / d_vox (int64 device tensors holding u64 words, set to ~0 once by the caller), distinct.  The
+    listed rows are lowered in place to the lexicographic minimum of what came in and what the box holds; nothing is returned and
+    nothing waits for the device."""
+    t, P = eng.torch, eng.ptr
+    ex, ey, ez = (int(v) for v in extent)
+    lox, loy, loz = (int(v) for v in lo)
+    _, dsy, dsz = (int(v) for v in dataset_shape)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    query_start = np.ascontiguousarray(query_start, dtype=np.uint32)
+    centroids = np.ascontiguousarray(centroids, dtype=np.float64).reshape(-1, 3)
+    query_index = np.ascontiguousarray(query_index, dtype=np.uint32)
+    nq = int(centroids.shape[0])
+    assert words.size >= 1 and query_start.size == words.size + 1 and int(query_start[-1]) == nq and nq >= 1
+    assert np.all(words[1:] > words[:-1])
+    assert query_index.size == nq and np.unique(query_index).size == nq and int(query_index.max()) < min(d_best.numel(), d_vox.numel())
+    assert int(d_lab.numel()) == ex * ey * ez and d_lab.element_size() == label_bytes
+    if not np.all(np.isfinite(centroids)):
+        raise ValueError("centroids must be finite")
+    d_words = t.from_numpy(words.view(np.int64)).to(eng.device)
+    d_start = t.from_numpy(query_start.view(np.int32)).to(eng.device)
+    d_cen = t.from_numpy(centroids).to(eng.device)
+    d_index = t.from_numpy(query_index.view(np.int32)).to(eng.device)
+    d_scratch = eng.empty(nq, t.int64)
+    _abi.check(eng.lib.kh_nearest_label_voxels_box(P(d_lab), label_bytes, ex, ey, ez, lox, loy, loz, dsy, dsz, P(d_words), P(d_start),
+                                                   int(words.size), P(d_cen), P(d_index), nq, P(d_best), P(d_vox), P(d_scratch),
+                                                   eng.stream()))
+
+
 def binary_edges(eng, d_img, shape, connectivity=26):
     """d_img: u8 device tensor [nvox] in Fortran order, foreground = 1 (0 / 1 only: the neighbour masks compare labels).
     Returns (vertices u32 (n, 3), edges u32 (m, 2)) as host arrays in the canonical order: vertices by ascending Fortran index,
