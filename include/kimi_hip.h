@@ -676,6 +676,9 @@ int64_t kh_host_ccl26(const void* labels, int label_bytes, int64_t sx, int64_t s
  * compute_centroids :528-588 and compute_tiebreaker_maxima :650-760) on HOST memory.
  * dt (f32) and cc (u32) are [sx,sy] Fortran ordered planes; for each component id with a maximum
  * out_xy[2*id..2*id+1] receives (x, y) and `order` the ids in dict-insertion order.
+ * cc holds ids 0..nlab.  The caller sizes out_xy for 2 * (nlab + 1) floats -- the rows of id 0 and of ids
+ * without a maximum are not written -- and `order` for nlab + 1 entries, of which at most nlab are written
+ * (none when nlab is 0).
  * Returns the number of ids, -1 on allocation failure.                                  */
 int64_t kh_host_find_border_targets(const float* dt, const uint32_t* cc, int64_t sx, int64_t sy,
                                     float wx, float wy, int64_t nlab, float* out_xy, int32_t* order);
