@@ -1,18 +1,23 @@
-"""What the dataset-in-boxes drivers share (section_boxes, segment_boxes, post.skeletonize_chunked): a dataset that is never resident
-as a whole is read box by box, and every driver needs the same plumbing around that.  Each piece has its one owner here:
+"""What the dataset-in-boxes drivers share (region_boxes, section_boxes, segment_boxes, point_boxes; post.skeletonize_chunked
+composes them): a dataset that is never resident as a whole is read box by box, and every driver needs the same plumbing around
+that.  Each piece has its one owner here:
 
     axes, label_type                   what a driver knows about its dataset: shape as given, with three axes, extent; dtype, span
     _slices, _load_box                 a box of a dataset or a store as a host array, optionally checked against the shape asked for
+    _store_box                         its writing counterpart: a host box into a dataset or a store
     store_like                         a store of the dataset's shape and one dtype: the caller's, checked, or a Fortran numpy array
     label_table                        the skeletons' labels, their sorted table and each label's place in it
     upload_labels                      a host box of labels -> the device labels the kernels read, and the word of every table entry
     count_core, count_core_device      voxels per label of the table in a core, on the host and on the device
     group_by_core                      items grouped by the core they fall into
     up, down                           Fortran host box of 32-bit words <-> flat device tensor; the core of a device box -> host
+    route_targets, count_labels        on a plan.chunk_grid: the extra targets of every box; voxels per label over the cores
 
 The grid arithmetic (which core holds a voxel, a core's neighbours) is plan's: core_of, core_index, neighbor_cores.  Nothing here
 decides an order of checks or names a driver: the drivers call these in their own order and pass their name where a message has one.
 """
+from collections import defaultdict
+
 import numpy as np
 
 from . import utility
@@ -55,6 +60,20 @@ def _load_box(dataset, lo, hi, name=None):
     if name is not None and cut.shape != tuple(int(b) - int(a) for a, b in zip(lo, hi)):
         raise ValueError("{}: dataset[{}:{}] has shape {}".format(name, [int(v) for v in lo], [int(v) for v in hi], cut.shape))
     return cut
+
+
+def _store_box(target, lo, hi, box):
+    """target[lo:hi] = box (a host array with three axes), for what _load_box reads: arrays and memmaps of two or three axes, a tensor
+    (the box goes to where it lives), anything that takes a tuple of slices"""
+    ndim = len(target.shape)
+    box = box.reshape(box.shape[:ndim])
+    if hasattr(target, "cpu") and hasattr(target, "numpy"):
+        import torch
+        signed = {"uint16": np.int16, "uint32": np.int32, "uint64": np.int64}.get(box.dtype.name)   # (as Engine.to_device moves words)
+        piece = torch.from_numpy(np.ascontiguousarray(box if signed is None else box.view(signed))).to(target.device)
+        target[_slices(lo, hi)[:ndim]] = piece if piece.dtype == target.dtype else piece.view(target.dtype)
+    else:
+        target[_slices(lo, hi)[:ndim]] = box
 
 
 def store_like(given, shape, dtype, name, spelled=None, zeros=False):
@@ -125,3 +144,31 @@ def down(d_box, ext, inner=None):
     if inner is None:
         return d_box.cpu().numpy().reshape(ext, order="F")
     return _device_core(d_box, ext, inner).contiguous().cpu().numpy().transpose(2, 1, 0)
+
+
+def route_targets(targets, grid, shape):
+    """Extra targets given as voxels of the dataset -> per chunk of `grid` the list of those its box contains, as (x, y, z) tuples
+    relative to the box's low corner.  A point on an overlap plane goes to both boxes.  Two coordinates get z = 0.  IndexError, naming
+    the point, for one outside a dataset of `shape`."""
+    shape = (tuple(int(v) for v in shape) + (1,))[:3]
+    out = [[] for _ in range(grid.box_lo.shape[0])]
+    for target in targets:
+        pt = tuple(int(v) for v in target)
+        if len(pt) == 2:
+            pt += (0,)
+        if len(pt) != 3 or any(not 0 <= v < s for v, s in zip(pt, shape)):
+            raise IndexError("point {} is outside a dataset of shape {}".format(tuple(target), shape))
+        p = np.asarray(pt, dtype=np.int64)
+        for k in np.flatnonzero(((grid.box_lo <= p) & (p < grid.box_hi)).all(axis=1)).tolist():
+            out[k].append(tuple(int(v) for v in p - grid.box_lo[k]))
+    return out
+
+
+def count_labels(dataset, grid):
+    """{label: voxels in the whole dataset}, zero included, from one pass over the cores of `grid` (they partition the dataset)"""
+    total = defaultdict(int)
+    for lo, hi in zip(grid.core_lo, grid.core_hi):
+        values, counts = np.unique(_load_box(dataset, lo, hi), return_counts=True)
+        for value, count in zip(values.tolist(), counts.tolist()):
+            total[value] += count
+    return dict(total)

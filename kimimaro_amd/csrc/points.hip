@@ -4,10 +4,9 @@
 //                             of that label nearest to the centroid -- scipy's cdist + np.argmin(axis=0) over
 //                             np.vstack((labels == label).nonzero()).T, for ALL labels and centroids in two passes over the volume
 //                             instead of one pass and one dense distance matrix per label.
-//   kh_nearest_label_voxels_box   the same two passes on ONE BOX of a dataset that is never resident as a whole, on running per-query
-//                             results that stay on the device from box to box (synapses_to_targets_chunked):
-//                             distances from dataset coordinates, the dataset's C-order index, and the carry rule -- a box that
-//                             lowers a query's distance discards the index earlier boxes found for it.
+//   kh_nearest_label_voxels_box   the same sweep (nearest_sweep, one body for both) on ONE BOX of a dataset that is never resident as
+//                             a whole, on running per-query results that stay on the device from box to box
+//                             (synapses_to_targets_chunked), with the carry rule between its passes.
 //   kh_binary_edge_count /    skeletontricks.extract_edges_from_binary_image (skeletontricks.pyx:1047-1086, skeletontricks.hpp:399-495)
 //   kh_binary_edge_emit       on the words of kh_neighbor_mask: count, (the caller's scan), emit -- in a canonical order instead of
 //                             the iteration order of an unordered_set.
@@ -38,99 +37,27 @@ __global__ void fill_u64_kernel(unsigned long long* p, int64_t n, unsigned long 
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// PASS 1: best_d[q] = min over the label's voxels of the bits of d (non-negative doubles order like u64).
-// PASS 2: best_c[q] = min C-order index x*sy*sz + y*sz + z over the label's voxels whose d has exactly those bits.
+// a voxel coordinate of nearest_sweep: in a dataset 64 bits, in a resident volume the int it is
+template <bool BOX>
+using coord_t = typename std::conditional<BOX, int64_t, int>::type;
+
+// ONE body for both nearest-voxel kernels: the sweep of a volume of extent (ex, ey, ez).
+// PASS 1: best_d[g] = min over the label's voxels of the bits of d (non-negative doubles order like u64).
+// PASS 2: best_c[g] = min C-order index X*dsy*dsz + Y*dsz + Z over the label's voxels whose d has exactly those bits.
 // A block walks a CONTIGUOUS range of x tiles (256 voxels of one row): a thread's next voxel is the one 256 further along the row or
 // the same x of the next row, which mostly carries the label it has just looked up -- the search of the table is then skipped.
-template <typename LT, int PASS>
-__global__ __launch_bounds__(256) void nearest_kernel(const LT* __restrict__ lab, int sx, int sy, int sz, int64_t tiles_per_block,
-                                                      const unsigned long long* __restrict__ table, const uint32_t* __restrict__ qstart,
-                                                      int nlab, const double* __restrict__ cen, unsigned long long* best_d,
-                                                      unsigned long long* best_c) {
-  const int xt = (sx + 255) >> 8;
-  const int64_t ntiles = (int64_t)xt * sy * sz;
-  const int64_t t0 = (int64_t)blockIdx.x * tiles_per_block;
-  const int64_t t1 = (t0 + tiles_per_block < ntiles) ? t0 + tiles_per_block : ntiles;
-  unsigned long long lastL = 0;
-  int lastSlot = -2;                      // -2: nothing looked up yet; -1: lastL is not in the table
-  for (int64_t t = t0; t < t1; t++) {
-    const int x = (int)(t % xt) * 256 + (int)threadIdx.x;
-    const int64_t r = t / xt;
-    const int y = (int)(r % sy), z = (int)(r / sy);
-    int slot = -1;
-    if (x < sx) {
-      const unsigned long long L = (unsigned long long)lab[x + (int64_t)sx * (y + (int64_t)sy * z)];
-      if (lastSlot == -2 || L != lastL) {
-        int lo = 0, hi = nlab;            // first entry >= L
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (table[mid] < L) lo = mid + 1; else hi = mid;
-        }
-        lastL = L;
-        lastSlot = (lo < nlab && table[lo] == L) ? lo : -1;
-      }
-      slot = lastSlot;
-    }
-    // the distinct labels of the wave, one after the other; the lanes of one label combine before anything goes to memory
-    unsigned long long todo = __ballot(slot >= 0);
-    while (todo) {
-      const int s = __shfl(slot, __ffsll((long long)todo) - 1);
-      const bool mine = slot == s;
-      todo &= ~__ballot(mine);
-      const uint32_t q0 = qstart[s], q1 = qstart[s + 1];
-      for (uint32_t q = q0; q < q1; q++) {
-        // scipy's euclidean kernel: s = 0; s += d*d per axis; sqrt(s) -- every operation rounded (no contraction in this library)
-        const double dx = (double)x - cen[3 * (size_t)q + 0];
-        const double dy = (double)y - cen[3 * (size_t)q + 1];
-        const double dz = (double)z - cen[3 * (size_t)q + 2];
-        const double d = __dsqrt_rn((dx * dx + dy * dy) + dz * dz);
-        const unsigned long long key = (unsigned long long)__double_as_longlong(d);
-        const unsigned long long cur = best_d[q];     // PASS 1: may be stale, i.e. too large -- costs an atomic, never a result
-        if (PASS == 1) {
-          if (!__any(mine && key < cur)) continue;
-          const unsigned long long m = wave_min_u64(mine ? key : ~0ull);
-          const unsigned long long holders = __ballot(mine && key == m);
-          if ((int)(threadIdx.x & 63) == __ffsll((long long)holders) - 1) atomicMin(&best_d[q], m);
-        } else {
-          const bool hit = mine && key == cur;
-          if (!__any(hit)) continue;
-          const unsigned long long c = ((unsigned long long)x * (unsigned long long)sy + (unsigned long long)y) * (unsigned long long)sz + (unsigned long long)z;
-          const unsigned long long m = wave_min_u64(hit ? c : ~0ull);
-          if (hit && c == m && m < best_c[q]) atomicMin(&best_c[q], m);
-        }
-      }
-    }
-  }
-}
-
-// ONE BOX of a dataset that is never resident as a whole: the two passes of nearest_kernel on a box of extent
-// (ex, ey, ez) whose low corner lies at (lox, loy, loz) of a dataset with y and z extents dsy, dsz.  Distances are taken from the
-// DATASET coordinates of a voxel, the index is the dataset's C-order index, and the results are RUNNING ones: query q of this visit
-// owns row qidx[q] of best_d / best_c, which come in holding the best of the boxes visited so far and are never filled here.
-//   carry_save   scratch[q] = best_d[qidx[q]]                        the distances that came in
-//   PASS 1       best_d[g] = min(itself, the box's distances)        as nearest_kernel
-//   carry_reset  best_c[g] = ~0 where best_d[g] != scratch[q]         a lowered distance makes the index of earlier boxes stale
-//   PASS 2       best_c[g] = min(itself, the box's indices at best_d[g])   an index that was kept competes with this box's
-__global__ void carry_save_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
-                                  unsigned long long* __restrict__ scratch) {
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) scratch[q] = best_d[qidx[q]];
-}
-
-__global__ void carry_reset_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
-                                   const unsigned long long* __restrict__ scratch, unsigned long long* __restrict__ best_c) {
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t g = qidx[q];
-    if (best_d[g] != scratch[q]) best_c[g] = ~0ull;
-  }
-}
-
-template <typename LT, int PASS>
-__global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__ lab, int ex, int ey, int ez, int64_t lox, int64_t loy,
-                                                          int64_t loz, int64_t dsy, int64_t dsz, int64_t tiles_per_block,
-                                                          const unsigned long long* __restrict__ table,
-                                                          const uint32_t* __restrict__ qstart, int nlab, const double* __restrict__ cen,
-                                                          const uint32_t* __restrict__ qidx, unsigned long long* best_d,
-                                                          unsigned long long* best_c) {
+// With BOX the volume is one box, low corner (lox, loy, loz), of a dataset with y and z extents dsy, dsz.  Three
+// things differ:
+//   the coordinate   distances and the index come from X = lox + x in the DATASET, 64 bits; without BOX lo is 0 and X stays the int x,
+//                    so that its conversion to double remains the 32-bit one
+//   the row          query q owns row g = qidx[q] of the running best_d / best_c; without BOX row q, and qidx is not read
+//   the extents      dsy, dsz of the index are the dataset's; without BOX the volume's own sy, sz
+template <typename LT, int PASS, bool BOX>
+__device__ __forceinline__ void nearest_sweep(const LT* __restrict__ lab, int ex, int ey, int ez, coord_t<BOX> lox, coord_t<BOX> loy,
+                                              coord_t<BOX> loz, coord_t<BOX> dsy, coord_t<BOX> dsz, int64_t tiles_per_block,
+                                              const unsigned long long* __restrict__ table, const uint32_t* __restrict__ qstart, int nlab,
+                                              const double* __restrict__ cen, const uint32_t* __restrict__ qidx, unsigned long long* best_d,
+                                              unsigned long long* best_c) {
   const int xt = (ex + 255) >> 8;
   const int64_t ntiles = (int64_t)xt * ey * ez;
   const int64_t t0 = (int64_t)blockIdx.x * tiles_per_block;
@@ -155,7 +82,8 @@ __global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__
       }
       slot = lastSlot;
     }
-    const int64_t X = lox + x, Y = loy + y, Z = loz + z;       // the voxel in the dataset
+    const coord_t<BOX> X = lox + x, Y = loy + y, Z = loz + z;       // the voxel in the dataset
+    // the distinct labels of the wave, one after the other; the lanes of one label combine before anything goes to memory
     unsigned long long todo = __ballot(slot >= 0);
     while (todo) {
       const int s = __shfl(slot, __ffsll((long long)todo) - 1);
@@ -163,7 +91,8 @@ __global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__
       todo &= ~__ballot(mine);
       const uint32_t q0 = qstart[s], q1 = qstart[s + 1];
       for (uint32_t q = q0; q < q1; q++) {
-        const uint32_t g = qidx[q];
+        const uint32_t g = BOX ? qidx[q] : q;
+        // scipy's euclidean kernel: s = 0; s += d*d per axis; sqrt(s) -- every operation rounded (no contraction in this library)
         const double dx = (double)X - cen[3 * (size_t)q + 0];
         const double dy = (double)Y - cen[3 * (size_t)q + 1];
         const double dz = (double)Z - cen[3 * (size_t)q + 2];
@@ -185,6 +114,43 @@ __global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__
       }
     }
   }
+}
+
+template <typename LT, int PASS>
+__global__ __launch_bounds__(256) void nearest_kernel(const LT* __restrict__ lab, int sx, int sy, int sz, int64_t tiles_per_block,
+                                                      const unsigned long long* __restrict__ table, const uint32_t* __restrict__ qstart,
+                                                      int nlab, const double* __restrict__ cen, unsigned long long* best_d,
+                                                      unsigned long long* best_c) {
+  nearest_sweep<LT, PASS, false>(lab, sx, sy, sz, 0, 0, 0, sy, sz, tiles_per_block, table, qstart, nlab, cen, nullptr, best_d, best_c);
+}
+
+// The running results of a dataset in boxes: best_d / best_c come in holding the best of the boxes visited so far and are never
+// filled here.
+//   carry_save   scratch[q] = best_d[qidx[q]]                        the distances that came in
+//   PASS 1       best_d[g] = min(itself, the box's distances)        nearest_sweep<.., 1, true>
+//   carry_reset  best_c[g] = ~0 where best_d[g] != scratch[q]         a lowered distance makes the index of earlier boxes stale
+//   PASS 2       best_c[g] = min(itself, the box's indices at best_d[g])   an index that was kept competes with this box's
+__global__ void carry_save_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
+                                  unsigned long long* __restrict__ scratch) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) scratch[q] = best_d[qidx[q]];
+}
+
+__global__ void carry_reset_kernel(const uint32_t* __restrict__ qidx, int64_t nq, const unsigned long long* __restrict__ best_d,
+                                   const unsigned long long* __restrict__ scratch, unsigned long long* __restrict__ best_c) {
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
+    const uint32_t g = qidx[q];
+    if (best_d[g] != scratch[q]) best_c[g] = ~0ull;
+  }
+}
+
+template <typename LT, int PASS>
+__global__ __launch_bounds__(256) void nearest_box_kernel(const LT* __restrict__ lab, int ex, int ey, int ez, int64_t lox, int64_t loy,
+                                                          int64_t loz, int64_t dsy, int64_t dsz, int64_t tiles_per_block,
+                                                          const unsigned long long* __restrict__ table,
+                                                          const uint32_t* __restrict__ qstart, int nlab, const double* __restrict__ cen,
+                                                          const uint32_t* __restrict__ qidx, unsigned long long* best_d,
+                                                          unsigned long long* best_c) {
+  nearest_sweep<LT, PASS, true>(lab, ex, ey, ez, lox, loy, loz, dsy, dsz, tiles_per_block, table, qstart, nlab, cen, qidx, best_d, best_c);
 }
 
 // the 13 directions of dir_delta whose neighbour comes LATER in the Fortran raster, as a mask

@@ -202,9 +202,9 @@ def test_counts_are_summed_in_64_bits_and_refused_only_where_they_matter():
 def test_no_cpu_fallback_without_the_hooks():
     import torch
     import kimimaro_amd
-    from kimimaro_amd import section_boxes
-    assert kimimaro_amd.fill_all_holes_chunked is post.fill_all_holes_chunked is section_boxes.fill_all_holes_chunked
-    assert post.fill_all_holes_chunked.__module__ == "kimimaro_amd.section_boxes"
+    from kimimaro_amd import region_boxes
+    assert kimimaro_amd.fill_all_holes_chunked is post.fill_all_holes_chunked is region_boxes.fill_all_holes_chunked
+    assert post.fill_all_holes_chunked.__module__ == "kimimaro_amd.region_boxes"
     if torch.cuda.is_available():
         return
     with pytest.raises(kimimaro_amd.HipUnavailableError):

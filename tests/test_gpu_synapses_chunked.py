@@ -165,6 +165,33 @@ def test_lane_boundaries_and_label_widths(eng, dtype):
     assert (vox == S.NONE64).sum() == 5                                    # base + 3 does not occur
 
 
+def test_blocks_of_several_tiles_by_both_entry_points(eng):
+    """a box of 2 x 65 x 64 = 8 320 x tiles: the launch is capped at 4 096 blocks, so a block walks 3 tiles (2 774 blocks, the last one
+    short) and carries its looked-up label from tile to tile; the second tile of every row has one lane inside the box (x = 256).
+    The whole-volume entry and the box entry at lo = 0 with an identity query_index run the one sweep and must agree"""
+    from kimimaro_amd import points
+    shape = (257, 65, 64)
+    assert -(-shape[0] // 256) * shape[1] * shape[2] == 8320 and -(-8320 // 4096) == 3 and -(-8320 // 3) == 2774
+    box = np.empty(shape, dtype=np.uint16, order="F")
+    box[:, :20], box[:, 20:45], box[:, 45:] = 500, 501, 502                # slabs along y: a row's label is its neighbour's, mostly
+    box[100:140, 18:24, 30:] = 503                                         # an island across a slab boundary
+    box[256, 7:60, 3:50] = 504                                             # a label confined to x >= 256, the lone lane of its tile
+    rng = np.random.default_rng(23)
+    synapses = {label: [(tuple((rng.integers(-8 * 6, 8 * (np.array(shape) + 6)) / 8.0).tolist()), 0) for _ in range(5)]
+                for label in (500, 501, 502, 503, 504, 505)}               # 505 occurs nowhere
+    queries = queries_of(synapses, (0, 65535), 2)
+    want = fresh(30)
+    S.visit(box, (0, 0, 0), shape, *queries, *want)
+    assert (want[1] == S.NONE64).sum() == 5 and (want[1][20:25] // (shape[1] * shape[2]) == 256).all()
+    dist, vox = fresh(30)
+    kernel_visit(eng, box, (0, 0, 0), shape, *queries, dist, vox)
+    winners = points.nearest_label_voxels(eng, eng.to_device(box), 2, shape, *queries[:3])
+    np.testing.assert_array_equal(dist, want[0])
+    np.testing.assert_array_equal(vox, want[1])
+    np.testing.assert_array_equal(winners, want[1])
+    np.testing.assert_array_equal(winners, vox)
+
+
 def test_indices_beyond_2_to_the_32(eng):
     shape = (2 ** 21 + 8, 2 ** 20, 2 ** 20)
     lo = (2 ** 21, 2 ** 20 - 8, 2 ** 20 - 8)

@@ -11,7 +11,8 @@ PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 
 
 # low to high: a module imports, at module level, only modules in front of it
 ORDER = ("_abi", "skeleton", "build", "plan", "volume", "holes", "border", "assemble", "engine", "feature", "points", "section",
-         "ops", "trace", "avocado", "intake", "utility", "lanes", "distributed", "boxes", "section_boxes", "segment_boxes", "post")
+         "ops", "trace", "avocado", "intake", "utility", "lanes", "distributed", "boxes", "region_boxes", "section_boxes", "segment_boxes",
+         "point_boxes", "post")
 
 # name -> the module that defines it; each is the same object as kimimaro_amd.intake.NAME
 LEGACY = {
@@ -28,7 +29,10 @@ LEGACY = {
 
 # name -> the module that defines it; each is the same object as kimimaro_amd.post.NAME
 POST = {
-    "region_graph_chunked": "section_boxes", "hole_lists": "section_boxes", "RegionGraph": "section_boxes",
+    "region_graph_chunked": "region_boxes", "hole_lists": "region_boxes", "RegionGraph": "region_boxes", "_merge_regions": "region_boxes",
+    "fill_all_holes_chunked": "region_boxes",
+    "synapses_to_targets_chunked": "point_boxes",
+    "route_targets": "boxes", "count_labels": "boxes",
     "cross_sectional_area_chunked": "section_boxes", "cross_sectional_area_filled_chunked": "section_boxes", "XS_CLIPPED": "section_boxes",
     "oversegment_chunked": "segment_boxes", "shell_diff": "segment_boxes", "DIRECTIONS": "segment_boxes",
 }
