@@ -726,6 +726,23 @@ int kh_part_gaps(const float* xyz, const uint32_t* part_start, const float* part
                  const double* bound2, const int64_t* rec_start, int64_t ngroups, int64_t nrecords, uint64_t* rec_d2,
                  uint32_t* rec_idx, void* stream);
 
+/* ---- row f4 on the device, the broad phase in front of kh_part_gaps: the sets of parts of a group that are
+ * connected through near pairs.  Parts t != q of one group g are NEAR iff low(t, q) < bound2[g], where low = (gx*gx + gy*gy) + gz*gz
+ * and g. is the distance of the two parts' intervals along an axis (0 where they overlap), taken on the part_box floats widened to
+ * f64, every operation rounded in f64, no FMA: the very quantity on which kh_part_gaps declares a pair "none" without a look at
+ * its vertices (one device function serves both), so a pair that has a record is near.  cluster[p] = the smallest part index, in
+ * the numbering of part_box, among the parts connected to p through near pairs; a part alone is its own cluster, parts of
+ * different groups are never connected, with bound2 = +inf a group is one cluster.  A function of the boxes alone.
+ * Device inputs: part_box f32 [P,6], group_start u32 [G+1], bound2 f64 [G] as for kh_part_gaps; order u32 [P]: at the positions
+ * [group_start[g], group_start[g+1]) the parts of group g sorted by part_box[.][axis] ascending, ties by part index; axis 0, 1 or 2.
+ * The result does not depend on the axis.  An entry of order outside its group is skipped (its part then joins nothing by it).
+ * Output: cluster u32 [P], every word written; it doubles as the parent array of the union-find, so the library allocates
+ * nothing and no list of pairs is stored.  Three launches (identity, unions, flatten), asynchronous on `stream`.
+ * Cost: a part is tested against the later parts of `order` up to the first whose low end lies the bound beyond its high end:
+ * at worst n_g^2 / 2 box tests for a group whose boxes all span the axis.  0 <= G, P < 2^31.                                     */
+int kh_part_clusters(const float* part_box, const uint32_t* group_start, const double* bound2, const uint32_t* order,
+                     int64_t ngroups, int64_t nparts, int axis, uint32_t* cluster, void* stream);
+
 /* ---- row f4 (host side, no GPU): the merge plan of join_close_components (kimimaro/post.py:89-218) for ONE group, reading only
  * the table of its nparts parts: rec_d2 [nparts*nparts], rec_idx [nparts*nparts,2] as above; part_size [nparts]; radii = the
  * parts' vertex radii back to back; radius = the value the search ends up with (with restrict_by_radius: twice the largest

@@ -27,7 +27,7 @@ SYMBOLS = [
     "kh_cross_sections_box", "kh_cross_sections_fixed_exponent", "kh_cross_sections_filled_box",
     "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
     "kh_region_table_box", "kh_region_seam_pairs", "kh_region_apply_box",
-    "kh_part_gaps", "kh_host_join_plan",
+    "kh_part_gaps", "kh_part_clusters", "kh_host_join_plan",
     "kh_heap_script",
 ]
 
@@ -198,6 +198,7 @@ def lib():
     L.kh_host_enclosed_regions.argtypes = [i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]
     L.kh_host_enclosed_regions.restype = i64
     L.kh_part_gaps.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
+    L.kh_part_clusters.argtypes = [vp, vp, vp, vp, i64, i64, ci, vp, vp]
     L.kh_host_join_plan.argtypes = [i64, vp, vp, vp, vp, f64, ci, vp]
     L.kh_host_join_plan.restype = i64
     L.kh_heap_script.argtypes = [ci, vp, i64, vp, i64, C.c_uint32, vp, i64, vp, i64, vp, vp]

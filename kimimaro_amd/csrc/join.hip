@@ -5,6 +5,8 @@
 //                       (d2, kq, kt) over the vertices of both -- what kimimaro/post.py:89-218 asks of one cKDTree per part, again
 //                       after every merge, computed once for all original parts of all groups.
 //   kh_host_join_plan   host C, no GPU: the merge sequence of join_close_components on one group, reading only that table.
+//   kh_part_clusters    the broad phase in front of both: the sets of parts of a group that are connected through pairs of boxes
+//                       nearer than the bound.  No record and no merge crosses two of them, so each is a join of its own.
 //
 // One workgroup per unordered pair.  A lane owns a vertex of the larger part ("own" side, 256 per slab) and walks the other part in
 // ascending index from LDS tiles -- every lane reads the same address, a broadcast -- keeping with a strict < its nearest other
@@ -47,6 +49,14 @@ __device__ __forceinline__ double axis_gap(double lo_a, double hi_a, double lo_b
   const double g1 = lo_a - hi_b, g2 = lo_b - hi_a;
   const double g = g1 > g2 ? g1 : g2;
   return g > 0.0 ? g : 0.0;
+}
+
+// a lower bound of every d2 between the vertices of two parts, from their boxes (min x, y, z, max x, y, z), formed with the operations
+// of the vertex loop (differences, squares and sums of f64 are monotone).  The ONE statement of it: part_gaps_kernel culls a pair on
+// box_gap2 >= bound2, part_clusters_kernel calls a pair near on box_gap2 < bound2, so "near" covers "has a record" by construction.
+__device__ __forceinline__ double box_gap2(const float* a, const float* b) {
+  const double gx = axis_gap(a[0], a[3], b[0], b[3]), gy = axis_gap(a[1], a[4], b[1], b[4]), gz = axis_gap(a[2], a[5], b[2], b[5]);
+  return (gx * gx + gy * gy) + gz * gz;
 }
 
 __device__ __forceinline__ void gap_store(unsigned long long* rec_d2, uint32_t* rec_idx, int64_t cell, unsigned long long d2, uint32_t kt,
@@ -96,11 +106,8 @@ __global__ __launch_bounds__(256) void part_gaps_kernel(const float* __restrict_
   const float* by = part_box + 6 * (size_t)(p0 + Y);
   const double ylo0 = by[0], ylo1 = by[1], ylo2 = by[2], yhi0 = by[3], yhi1 = by[4], yhi2 = by[5];
   {
-    // a lower bound of every d2 of the pair, formed with the operations of the vertex loop (differences, squares and sums of f64 are
-    // monotone): at or above the bound the pair has no record
-    const double gx = axis_gap(bx[0], bx[3], ylo0, yhi0), gy = axis_gap(bx[1], bx[4], ylo1, yhi1), gz = axis_gap(bx[2], bx[5], ylo2, yhi2);
-    const double low = (gx * gx + gy * gy) + gz * gz;
-    if (low >= b2) {
+    // at or above the bound the pair has no record
+    if (box_gap2(bx, by) >= b2) {
       if (tid == 0) {
         gap_store(rec_d2, rec_idx, cell_own_query, GAP_INF, GAP_NONE, GAP_NONE, b2);
         gap_store(rec_d2, rec_idx, cell_own_tree, GAP_INF, GAP_NONE, GAP_NONE, b2);
@@ -173,9 +180,123 @@ __global__ __launch_bounds__(256) void part_gaps_kernel(const float* __restrict_
   }
 }
 
+// ---- the broad phase: connected sets of near parts ----------------------------------------------------------------
+// A union-find whose parent array IS the output.  parent[x] <= x always: a root is hooked under a smaller root only, by one integer
+// CAS that succeeds only while it still is a root, so the trees never form a cycle and, once every near pair has been united, the
+// root of a tree is the smallest part of its connected set -- whatever order the unions arrived in.  A parent word only ever moves to
+// another ancestor of its node, so a reader that sees an older value still walks to the root.  These are the only global atomics of
+// this file: 32-bit integers, one successful CAS per true union, and no floating-point value goes through them.
+__device__ __forceinline__ uint32_t uf_load(const uint32_t* parent, uint32_t x) {
+  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {      // with path halving
+  for (;;) {
+    const uint32_t p = uf_load(parent, x);
+    if (p == x) return x;
+    const uint32_t gp = uf_load(parent, p);
+    if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = gp;
+  }
+}
+
+__device__ __forceinline__ void uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a == b) return;
+    if (a < b) {
+      const uint32_t s = a;
+      a = b;
+      b = s;
+    }
+    if (atomicCAS(parent + a, a, b) == a) return;      // the larger root under the smaller; it was hooked meanwhile: walk on from both
+  }
+}
+
+__global__ __launch_bounds__(256) void part_clusters_init_kernel(uint32_t* __restrict__ cluster, uint32_t nparts) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p < nparts) cluster[p] = p;
+}
+
+// One wave per position s of `order`; its part i = order[s] is tested against the parts at the later positions of its group, lanes
+// strided over them.  lo along the sweep axis ascends with the position, so the first candidate j with g1 = lo_j - hi_i > 0 and
+// g1 * g1 >= bound2 ends the scan: for every later one g1 is no smaller, the axis term of box_gap2 is max(g1, .) squared, and the
+// sum of box_gap2 is no smaller than that term (the same f64 operations, all monotone) -- none of them is near.
+__global__ __launch_bounds__(256) void part_clusters_kernel(const float* __restrict__ part_box, const uint32_t* __restrict__ group_start,
+                                                            const double* __restrict__ bound2, const uint32_t* __restrict__ order,
+                                                            int ngroups, uint32_t nparts, int axis, uint32_t* cluster) {
+  const uint32_t s = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (s >= nparts) return;
+  int lo = 0, hi = ngroups - 1;               // the group of this position: the first g with group_start[g + 1] > s
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (group_start[mid + 1] <= s) lo = mid + 1; else hi = mid;
+  }
+  const uint32_t p0 = group_start[lo];
+  uint32_t p1 = group_start[lo + 1];
+  if (p1 > nparts) p1 = nparts;
+  if (s < p0 || s >= p1) return;
+  const uint32_t i = order[s];
+  if (i < p0 || i >= p1) return;              // not a part of this group: `order` is no permutation within the groups
+  const double b2 = bound2[lo];
+  const float* bi = part_box + 6 * (size_t)i;
+  const double hi_i = bi[3 + axis];
+  for (uint32_t base = s + 1; base < p1; base += 64u) {
+    const uint32_t c = base + lane;
+    bool stop = false;
+    if (c < p1) {
+      const uint32_t j = order[c];
+      if (j >= p0 && j < p1 && j != i) {
+        const float* bj = part_box + 6 * (size_t)j;
+        const double g1 = (double)bj[axis] - hi_i;
+        stop = g1 > 0.0 && g1 * g1 >= b2;
+        if (!stop && box_gap2(bi, bj) < b2) uf_unite(cluster, i, j);
+      }
+    }
+    if (__any(stop)) break;
+  }
+}
+
+__global__ __launch_bounds__(256) void part_clusters_flatten_kernel(uint32_t* cluster, uint32_t nparts) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= nparts) return;
+  uint32_t x = p;
+  for (;;) {                                  // read only: another lane may be storing the root of x into cluster[x] right now,
+    const uint32_t up = uf_load(cluster, x);  // which is an ancestor of x like the word it replaces
+    if (up == x) break;
+    x = up;
+  }
+  __hip_atomic_store(cluster + p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 }  // namespace kh
 
 using namespace kh;
+
+extern "C" int kh_part_clusters(const float* part_box, const uint32_t* group_start, const double* bound2, const uint32_t* order,
+                                int64_t ngroups, int64_t nparts, int axis, uint32_t* cluster, void* stream) {
+  if (int rc = require_device()) return rc;
+  if (ngroups < 0 || ngroups >= (1ll << 31) || nparts < 0 || nparts >= (1ll << 31) || axis < 0 || axis > 2) {
+    set_error("kh_part_clusters: 0 <= ngroups < 2^31, 0 <= nparts < 2^31, axis 0, 1 or 2");
+    return KH_EINVAL;
+  }
+  if (ngroups == 0 || nparts == 0) return KH_OK;
+  if (!part_box || !group_start || !bound2 || !order || !cluster) {
+    set_error("kh_part_clusters: null pointer");
+    return KH_EINVAL;
+  }
+  const unsigned n = (unsigned)nparts;
+  hipLaunchKernelGGL(part_clusters_init_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, cluster, n);
+  KH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(part_clusters_kernel, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, part_box, group_start, bound2, order,
+                     (int)ngroups, n, axis, cluster);
+  KH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(part_clusters_flatten_kernel, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, cluster, n);
+  KH_LAUNCH_CHECK();
+  return KH_OK;
+}
 
 extern "C" int kh_part_gaps(const float* xyz, const uint32_t* part_start, const float* part_box, const uint32_t* group_start,
                             const double* bound2, const int64_t* rec_start, int64_t ngroups, int64_t nrecords, uint64_t* rec_d2,

@@ -433,3 +433,17 @@ def component_gaps(parts, bound=np.inf):
     eng = engine()
     bound = float(bound)
     return points.part_gaps(eng, [verts], [bound * bound])[0]
+
+
+def component_clusters(parts, bound):
+    """The sets join_close_components_many(split=True) cuts ONE group into (kh_part_clusters): parts as in
+    component_gaps.  Returns cluster u32 [n]: for every part the smallest index among the parts connected to it through pairs whose
+    bounding boxes are nearer than `bound` (their box distance squared, in f64, below bound * bound).  A pair with a record in
+    component_gaps(parts, bound) is such a pair, so no record crosses two clusters."""
+    verts = [np.asarray(getattr(p, "vertices", p), dtype=np.float32).reshape(-1, 3) for p in parts]
+    eng = engine()
+    bound = float(bound)
+    if not verts:
+        return np.zeros(0, dtype=np.uint32)
+    _, _, boxes = points.part_boxes(verts)
+    return points.part_clusters(eng, boxes, [0, len(verts)], [bound * bound])

@@ -1,7 +1,8 @@
 """Device plumbing of the point queries: the voxel of a label nearest to a centroid (kimimaro_amd.intake.synapses_to_targets) and
 the edges of a binary image (kimimaro_amd.ops.extract_edges_from_binary_image), both csrc/points.hip, DESIGN.md 3.11, on
-whole-volume arrays resident in HBM; and the nearest vertex pairs between the parts of skeleton groups (part_gaps: csrc/join.hip,
-DESIGN.md 3.14; kimimaro_amd.post.join_close_components_many).  The library allocates nothing, the scratch is sized here."""
+whole-volume arrays resident in HBM; and the nearest vertex pairs between the parts of skeleton groups (part_gaps) with the sets
+of parts no such pair crosses (part_clusters): csrc/join.hip; kimimaro_amd.post.join_close_components_many.  The
+library allocates nothing, the scratch is sized here."""
 from __future__ import annotations
 
 import time
@@ -163,6 +164,69 @@ def gap_launches(counts):
     return launches
 
 
+def part_boxes(parts):
+    """parts: vertex arrays f32 [k, 3], k >= 1 -> (xyz f32 [V, 3] back to back, part_start i64 [P + 1], box f32 [P, 6] = min x, y, z,
+    max x, y, z): the arrays kh_part_gaps and kh_part_clusters read"""
+    sizes = np.array([p.shape[0] for p in parts], dtype=np.int64)
+    if sizes.min() < 1:
+        raise ValueError("a part without vertices")
+    if int(sizes.sum()) >= 2 ** 32:
+        raise ValueError("the parts of one call hold %d vertices, more than 2^32 - 1" % int(sizes.sum()))
+    part_start = np.concatenate([[0], np.cumsum(sizes)])
+    xyz = np.concatenate(parts, axis=0)
+    box = np.concatenate([np.minimum.reduceat(xyz, part_start[:-1], axis=0), np.maximum.reduceat(xyz, part_start[:-1], axis=0)], axis=1)
+    return xyz, part_start, np.ascontiguousarray(box, dtype=np.float32)
+
+
+def sweep_order(boxes, group_start, axis):
+    """the `order` of kh_part_clusters: per group its parts by the low end of their box along `axis`, ties by part index"""
+    n = int(boxes.shape[0])
+    group_of = np.repeat(np.arange(group_start.size - 1), np.diff(group_start))
+    return np.lexsort((np.arange(n), boxes[:, axis], group_of)).astype(np.uint32)
+
+
+def part_clusters(eng, boxes, group_start, bound2, axis=None, timings=None):
+    """boxes: f32 [n, 6], the bounding boxes (min x, y, z, max x, y, z) of the parts of all groups, group after group; group_start:
+    [G + 1], indexing parts; bound2: f64 [G].  Returns cluster u32 [n] (kh_part_clusters, include/kimi_hip.h): the smallest part
+    index, in this call's numbering, among the parts connected to the part through pairs of ONE group whose boxes are nearer than
+    the group's bound.  One call for all groups.  axis: the axis the parts are swept along (None: the one over which the boxes' low
+    ends spread most, summed over the groups); the result does not depend on it.  timings (a dict): cluster_ms (HIP events) is
+    added to."""
+    t, P = eng.torch, eng.ptr
+    boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    group_start = np.ascontiguousarray(group_start, dtype=np.int64)
+    bound2 = np.ascontiguousarray(bound2, dtype=np.float64)
+    n, ngroups = int(boxes.shape[0]), int(bound2.size)
+    if group_start.size != ngroups + 1 or int(group_start[0]) != 0 or int(group_start[-1]) != n or np.any(np.diff(group_start) < 0):
+        raise ValueError("part_clusters: group_start must ascend from 0 to the %d parts for %d groups" % (n, ngroups))
+    if n >= 2 ** 31:
+        raise ValueError("part_clusters: %d parts, more than 2^31 - 1" % n)
+    if n == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if axis is None:
+        filled = group_start[:-1][np.diff(group_start) > 0]
+        low = boxes[:, :3].astype(np.float64)
+        axis = int(np.argmax((np.maximum.reduceat(low, filled, axis=0) - np.minimum.reduceat(low, filled, axis=0)).sum(axis=0)))
+    axis = int(axis)
+    if axis not in (0, 1, 2):
+        raise ValueError("part_clusters: axis must be 0, 1 or 2")
+    order = sweep_order(boxes, group_start, axis)
+    d_box = t.from_numpy(boxes).to(eng.device)
+    d_gstart = t.from_numpy(group_start.astype(np.uint32).view(np.int32)).to(eng.device)
+    d_bound = t.from_numpy(bound2).to(eng.device)
+    d_order = t.from_numpy(order.view(np.int32)).to(eng.device)
+    d_cluster = eng.empty(n, t.int32)
+    if timings is not None:
+        begin, end = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        begin.record()
+    _abi.check(eng.lib.kh_part_clusters(P(d_box), P(d_gstart), P(d_bound), P(d_order), ngroups, n, axis, P(d_cluster), eng.stream()))
+    if timings is not None:
+        end.record()
+        end.synchronize()
+        timings["cluster_ms"] = timings.get("cluster_ms", 0.0) + begin.elapsed_time(end)
+    return d_cluster.cpu().numpy().view(np.uint32)
+
+
 def part_gaps(eng, groups, bound2, timings=None):
     """groups: per group the list of its parts' vertices (f32 [k, 3], k >= 1); bound2: per group the f64 bound on d2 (+inf: none).
     Returns per group (d2 f64 [n, n], idx u32 [n, n, 2]): the records of kh_part_gaps (include/kimi_hip.h), row = tree part, column =
@@ -180,18 +244,11 @@ def part_gaps(eng, groups, bound2, timings=None):
             for g in launch:
                 out[g] = np.zeros((0, 0), dtype=np.float64), np.zeros((0, 0, 2), dtype=np.uint32)
             continue
-        sizes = np.array([p.shape[0] for p in parts], dtype=np.int64)
-        if sizes.min() < 1:
-            raise ValueError("a part without vertices")
-        if int(sizes.sum()) >= 2 ** 32:
-            raise ValueError("the parts of one call hold %d vertices, more than 2^32 - 1" % int(sizes.sum()))
-        part_start = np.concatenate([[0], np.cumsum(sizes)])
-        xyz = np.concatenate(parts, axis=0)
-        box = np.concatenate([np.minimum.reduceat(xyz, part_start[:-1], axis=0), np.maximum.reduceat(xyz, part_start[:-1], axis=0)], axis=1)
+        xyz, part_start, box = part_boxes(parts)
         group_start = np.concatenate([[0], np.cumsum(counts)])
         d_xyz = t.from_numpy(xyz).to(eng.device)
         d_pstart = t.from_numpy(part_start.astype(np.uint32).view(np.int32)).to(eng.device)
-        d_box = t.from_numpy(np.ascontiguousarray(box, dtype=np.float32)).to(eng.device)
+        d_box = t.from_numpy(box).to(eng.device)
         d_gstart = t.from_numpy(group_start.astype(np.uint32).view(np.int32)).to(eng.device)
         d_bound = t.from_numpy(np.array([bound2[g] for g in launch], dtype=np.float64)).to(eng.device)
         d_rstart = t.from_numpy(rec_start).to(eng.device)

@@ -4,7 +4,8 @@
     join_close_components(skeletons, radius=inf, restrict_by_radius)    kimimaro/post.py:89-218
     remove_dust / remove_loops / remove_ticks                            kimimaro/post.py:222-260, 436-563
 
-    join_close_components_many(groups, radius=inf, restrict_by_radius)  the join of many groups at once
+    join_close_components_many(groups, radius=inf, restrict_by_radius)  the join of many groups at once,
+    split_by_cluster, lift_edges                                        a group cut into the clusters that join independently
     postprocess_many(skeletons, dust_threshold=1500, tick_threshold=3000)
     skeletonize_chunked(dataset, chunk_shape, ...)                      a dataset in chunks to whole skeletons,
     place_fragment                                                      which composes postprocess_many with every box driver
@@ -22,7 +23,8 @@ imported here, so that every name stays reachable as kimimaro_amd.post.NAME (als
 Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
 functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
 come from one kernel call (csrc/join.hip through kimimaro_amd.points.part_gaps), the merge sequence from host C that reads only
-that table (kh_host_join_plan); they have no CPU fallback.  Written from the behaviour of the reference, including the parts that are visible in its
+that table (kh_host_join_plan), a group too large for one table is cut into independent clusters by a third (kh_part_clusters
+through points.part_clusters); they have no CPU fallback.  Written from the behaviour of the reference, including the parts that are visible in its
 results: which cycle its depth-first search reports first (skeletontricks.hpp:209-300: neighbours in the order the
 edges list them, the search starts at the first edge), float32 branch lengths accumulated outward from the smallest
 terminal node (skeletontricks.hpp:303-380), superedges fused at a branch point that drops to two edges and from then
@@ -162,14 +164,55 @@ def join_plan(part_sizes, d2, idx, radii, radius, restrict_by_radius):
     return edges[:m]
 
 
-def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, timings=None):
+def split_by_cluster(parts, cluster):
+    """parts: the parts of ONE group; cluster: an id per part, equal for the parts of one cluster (any integers: the ids of
+    kh_part_clusters are part numbers of a whole call).  Returns the sub-groups of the group, one per cluster of at least two parts,
+    as a list of (members, their parts): members = the int64 indices into `parts` of the cluster's parts, ascending; the sub-groups
+    are ordered by their first member.  A part alone in its cluster joins nothing and appears in no sub-group."""
+    cluster = np.asarray(cluster).reshape(-1)
+    if cluster.size != len(parts):
+        raise ValueError("split_by_cluster: %d cluster ids for %d parts" % (cluster.size, len(parts)))
+    if cluster.size == 0:
+        return []
+    by_id = np.argsort(cluster, kind="stable")           # the parts of a cluster next to each other, ascending among themselves
+    cuts = np.flatnonzero(np.diff(cluster[by_id]) != 0) + 1
+    runs = [run.astype(np.int64) for run in np.split(by_id, cuts) if run.size >= 2]
+    runs.sort(key=lambda run: int(run[0]))
+    return [(run, [parts[k] for k in run.tolist()]) for run in runs]
+
+
+def lift_edges(edges, members, part_sizes):
+    """edges: u32 [m, 2] in the numbering of a sub-group's concatenated parts (join_plan on the sub-group); members: the sub-group's
+    parts as indices into the group (split_by_cluster); part_sizes: vertices per part of the GROUP.  Returns the same edges, u32
+    [m, 2], in the numbering of the group's concatenated parts."""
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    members = np.asarray(members, dtype=np.int64).reshape(-1)
+    sizes = np.asarray(part_sizes, dtype=np.int64).reshape(-1)
+    first = np.concatenate([[0], np.cumsum(sizes)])      # of every part in the group's numbering
+    own = np.concatenate([[0], np.cumsum(sizes[members])])          # of every member in the sub-group's
+    if edges.size and (edges.min() < 0 or edges.max() >= own[-1]):
+        raise ValueError("lift_edges: an edge names a vertex outside the sub-group's %d vertices" % int(own[-1]))
+    k = np.searchsorted(own, edges, side="right") - 1    # the member a vertex belongs to (members are not empty)
+    return (first[members[k]] + (edges - own[k])).astype(np.uint32).reshape(-1, 2)
+
+
+def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, timings=None, split=None):
     """join_close_components for many groups at once: each group is a Skeleton or a sequence of them, the result per
     group what join_close_components(group, radius, restrict_by_radius) returns -- Skeleton.simple_merge of its parts plus one edge
     per merge, consolidated.  The nearest pairs between the parts of ALL groups come from one kernel call (a few when their tables
-    exceed 1 GiB; a single group of more than 8 192 parts is a ValueError), every group with its own radius and bound under
-    restrict_by_radius; the merge sequence of a group is decided on its table alone.  Where several tree vertices are equally near
-    the winning query vertex the smallest index is taken (cKDTree makes its own choice there).  No CPU fallback:
-    HipUnavailableError without the library or an MI355X.  timings (a dict): kernel_ms, copy_s, plan_s of the call."""
+    exceed 1 GiB), every group with its own radius and bound under restrict_by_radius; the merge sequence of a group is decided on
+    its table alone.  Where several tree vertices are equally near the winning query vertex the smallest index is taken (cKDTree
+    makes its own choice there).  No CPU fallback: HipUnavailableError without the library or an MI355X.
+
+    split: a group with a finite bound may first be cut into the sets of parts that are connected through pairs of boxes nearer than
+    its bound (kh_part_clusters, one call for all such groups); every set of two or more parts is then joined as a group of its
+    own, with the radius and bound of the WHOLE group, in the same kernel calls as the other groups, and its edges are put back.
+    The result is the same (no record and no merge crosses two sets), the tables are the sets' squares instead of the group's.
+    None (default): only the groups of more than 8 192 parts, which have no table of their own; True: every group with a finite
+    bound; False: none.  A set of more than 8 192 parts is a ValueError, and so is a group of that size that is not split (an
+    infinite radius, or split=False).
+    timings (a dict): kernel_ms, copy_s, plan_s of the call; cluster_ms (HIP events around kh_part_clusters), clusters (the sets of
+    two or more parts that were joined on their own) and largest_cluster (parts in the largest set; 0 when nothing was split)."""
     if radius is None:
         radius = np.inf
     if radius <= 0:
@@ -180,19 +223,49 @@ def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, 
     radius_of = [float(radius)] * len(groups)
     if restrict_by_radius:
         radius_of = [max(2 * max(float(np.max(p.radii)) for p in ps), 0) if ps else 0.0 for ps in parts]
+    bound2_of = [(r + 0.000001) * (r + 0.000001) for r in radius_of]
     todo = [g for g in range(len(groups)) if len(parts[g]) >= 2]
-    tables = points.part_gaps(eng, [[p.vertices for p in parts[g]] for g in todo],
-                              [(radius_of[g] + 0.000001) * (radius_of[g] + 0.000001) for g in todo], timings=timings)
-    out = [ps[0] if ps else Skeleton() for ps in parts]
+    cut = [g for g in todo if split is not False and np.isfinite(bound2_of[g])
+           and (split or len(parts[g]) > points.GAP_MAX_PARTS)]
+    members_of = {}                                      # group -> the members of its sub-groups
+    clusters = largest = 0
+    cluster_ms = {}
+    if cut:
+        _, _, boxes = points.part_boxes([p.vertices for g in cut for p in parts[g]])
+        group_start = np.concatenate([[0], np.cumsum([len(parts[g]) for g in cut])])
+        cluster = points.part_clusters(eng, boxes, group_start, [bound2_of[g] for g in cut], timings=cluster_ms)
+        for k, g in enumerate(cut):
+            ids = cluster[group_start[k]:group_start[k + 1]]
+            members_of[g] = [members for members, _ in split_by_cluster(parts[g], ids)]
+            sizes = np.unique(ids, return_counts=True)[1]
+            if int(sizes.max()) > points.GAP_MAX_PARTS:
+                raise ValueError("group %d: a cluster of %d parts connected through pairs nearer than the bound %r: more than %d, whose "
+                                 "table of nearest pairs exceeds 1 GiB" % (g, int(sizes.max()), radius_of[g] + 0.000001,
+                                                                           points.GAP_MAX_PARTS))
+            clusters += len(members_of[g])
+            largest = max(largest, int(sizes.max()))
+    # what is joined on a table of its own: (group, None) for a whole group, (group, members) for a sub-group
+    units = [(g, members) for g in todo for members in members_of.get(g, [None])]
+    tables = points.part_gaps(eng, [[p.vertices for p in (parts[g] if members is None else [parts[g][k] for k in members.tolist()])]
+                                    for g, members in units], [bound2_of[g] for g, _ in units], timings=timings)
     t0 = time.perf_counter()
-    for g, (d2, idx) in zip(todo, tables):
-        ps = parts[g]
-        merged = Skeleton.simple_merge(ps)
-        added = join_plan([p.vertices.shape[0] for p in ps], d2, idx, merged.radii, radius_of[g], restrict_by_radius)
-        merged.edges = np.concatenate([merged.edges, added])
+    added = {g: [] for g in todo}
+    sizes_of = {g: np.array([p.vertices.shape[0] for p in parts[g]], dtype=np.int64) for g in todo}
+    for (g, members), (d2, idx) in zip(units, tables):
+        ps = parts[g] if members is None else [parts[g][k] for k in members.tolist()]
+        edges = join_plan(sizes_of[g] if members is None else sizes_of[g][members], d2, idx, np.concatenate([p.radii for p in ps]),
+                          radius_of[g], restrict_by_radius)
+        added[g].append(edges if members is None else lift_edges(edges, members, sizes_of[g]))
+    out = [ps[0] if ps else Skeleton() for ps in parts]
+    for g in todo:
+        merged = Skeleton.simple_merge(parts[g])
+        merged.edges = np.concatenate([merged.edges] + added[g])
         out[g] = merged.consolidate(remove_disconnected_vertices=True)
     if timings is not None:
         timings["plan_s"] = timings.get("plan_s", 0.0) + time.perf_counter() - t0
+        timings["cluster_ms"] = timings.get("cluster_ms", 0.0) + cluster_ms.get("cluster_ms", 0.0)
+        timings["clusters"] = timings.get("clusters", 0) + clusters
+        timings["largest_cluster"] = max(timings.get("largest_cluster", 0), largest)
     return out
 
 
