@@ -315,6 +315,25 @@ int kh_invalidate_ball(kh_label_t* task, const uint32_t* lists, const uint32_t* 
 int kh_heap_script(int topl, const uint32_t* ops, int64_t nops, void* nodes, int64_t nodes_allocated, uint32_t capacity,
                    uint32_t* pops, int64_t pops_capacity, uint32_t* dumps, int64_t dumps_capacity, uint32_t* state, void* stream);
 
+/* ---- the flood on that heap on its own (csrc/heap.h, invalidate_ball): ONE call of the heap emulation of
+ * roll_invalidation_ball_inside_component by one workgroup of one wave, without the sweep, the ghosts and the scratch pool that
+ * surround it in kh_trace_paths and kh_invalidate_ball.  For tests; the product does not call it.
+ *   topl     1 or 2: the heap as for kh_heap_script (2 is the heap of KH_TRACE_BIG_LDS_HEAP); profile: 0, or 1 for the build that
+ *            KH_TRACE_PROFILE selects (the pop / push / neighbour-test cycle split).
+ *   sx, sy, sz, wx, wy, wz   the volume's extents and anisotropy.
+ *   nbrmask  the words of kh_neighbor_mask, or those words after kh_apply_voxel_graph; corner_gate: NULL, or the array
+ *            kh_apply_voxel_graph filled.  dbf: f32 per voxel.  alive: u8 per voxel, mutated in place like the reference's `labels`.
+ *   path     npath u32 linear indices of the sources (each below sx*sy*sz; the ball radius of source v is
+ *            f32(f32(scale * dbf[v]) + constant)); xmin, xmax: the x extent the degenerate corner entries are judged by (kh_label_t).
+ *   nodes, nodes_allocated, capacity   as for kh_heap_script: a push at n >= min(capacity, what a pop can descend through) is refused
+ *            and sets KH_ST_HEAP_OVERFLOW in the status word; nothing at or behind `capacity` is written.
+ *   state    three device words, written at the end: {voxels invalidated, pushes (refused ones included), status bits (KH_ST_*)}.
+ *   cyc3     three device uint64, written at the end: the cycles spent in pops, pushes and neighbour tests; all zero unless profile. */
+int kh_heap_flood(int topl, int profile, int64_t sx, int64_t sy, int64_t sz, float wx, float wy, float wz,
+                  const uint32_t* nbrmask, const uint8_t* corner_gate, const float* dbf, uint8_t* alive,
+                  const uint32_t* path, int64_t npath, float scale, float constant, uint32_t xmin, uint32_t xmax,
+                  void* nodes, int64_t nodes_allocated, uint32_t capacity, uint32_t* state, uint64_t* cyc3, void* stream);
+
 /* ---- a7 / a8 on their own: one search on one object (the path loop has them inside kh_trace_paths).
  * field: the weight volume (PDRF; +inf outside the object); dist: f32 volume, +inf on entry; qstate / queues as for
  * kh_edf_batch; task: the object's kh_label_t (q_offset / q_capacity, count).

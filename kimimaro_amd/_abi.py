@@ -28,7 +28,7 @@ SYMBOLS = [
     "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
     "kh_region_table_box", "kh_region_seam_pairs", "kh_region_apply_box",
     "kh_part_gaps", "kh_part_clusters", "kh_host_join_plan",
-    "kh_heap_script",
+    "kh_heap_script", "kh_heap_flood",
 ]
 
 
@@ -202,6 +202,8 @@ def lib():
     L.kh_host_join_plan.argtypes = [i64, vp, vp, vp, vp, f64, ci, vp]
     L.kh_host_join_plan.restype = i64
     L.kh_heap_script.argtypes = [ci, vp, i64, vp, i64, C.c_uint32, vp, i64, vp, i64, vp, vp]
+    L.kh_heap_flood.argtypes = [ci, ci, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, i64, f32, f32, C.c_uint32, C.c_uint32,
+                                vp, i64, C.c_uint32, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",

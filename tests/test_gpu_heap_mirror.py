@@ -37,13 +37,29 @@ def sources(shape):
     return [(sx // 4, sy // 4, sz // 4), (sx // 2, sy // 2, sz // 2), (3 * sx // 4, 3 * sy // 4, 3 * sz // 4)]
 
 
-def block_case(row, radii):
-    shape, an, r, regime = ROWS[row]
+def block_inputs(shape, r, radii):
+    """(sources, DBF) of a solid block: DBF = r everywhere, r times its factor at the three sources"""
     path = sources(shape)
     dbf = np.full(shape, r, np.float32, order="F")
     for (x, y, z), f in zip(path, RADII[radii]):
         dbf[x, y, z] = np.float32(r * f)
+    return path, dbf
+
+
+def block_case(row, radii):
+    shape, an, r, regime = ROWS[row]
+    path, dbf = block_inputs(shape, r, radii)
     return shape, an, path, dbf, regime
+
+
+def random_graph(shape, seed=77, cleared=0.05):
+    """a connectivity graph with every bit cleared independently (so asymmetrically: the reference reads only the word of the voxel
+    it expands)"""
+    rng = np.random.default_rng(seed)
+    vcg = np.full(shape, (1 << 26) - 1, dtype=np.uint32, order="F")
+    for b in range(26):
+        vcg &= ~(np.asfortranarray(rng.random(shape) < cleared).astype(np.uint32) << np.uint32(b))
+    return vcg
 
 
 def oracle_call(shape, an, path, dbf, graph=None):
@@ -88,10 +104,7 @@ def test_heap_mirror_voxel_graph(heap_ops, radii):
     """the (12, 12, 8) block with a random connectivity graph (bits cleared asymmetrically: the reference reads only the
     word of the voxel it expands): pushes are sparser, the heap still outgrows the mirror"""
     shape, an, path, dbf, _ = block_case("first_chunk", radii)
-    rng = np.random.default_rng(77)
-    vcg = np.full(shape, (1 << 26) - 1, dtype=np.uint32, order="F")
-    for b in range(26):
-        vcg &= ~(np.asfortranarray(rng.random(shape) < 0.05).astype(np.uint32) << np.uint32(b))
+    vcg = random_graph(shape)
     want_cnt, want, peak = oracle_call(shape, an, path, dbf, graph=vcg)
     print("graph/%s: oracle count %d, peak heap %d" % (radii, want_cnt, peak))
     assert MIRROR_END < peak < OLD_CHUNK, "the input left its regime: peak heap %d" % peak

@@ -8,7 +8,8 @@ array layout after every operation is identical to libstdc++'s"), the mirror wor
 and the state words.  The node buffer is filled with a sentinel and has 64 guard nodes behind it: slots below TOP (they live in
 LDS) and slots from max(capacity, TOP + 1) on must come back untouched.
 
-The batched append of invalidate_ball is not reached from here (it is part of the flood's loop): tests/test_gpu_heap_mirror.py and
+The batched append of invalidate_ball is not reached from here (it is part of the flood's loop): tests/test_gpu_heap_flood.py
+(kh_heap_flood, both heaps, at the sizes where the append's selects switch), tests/test_gpu_heap_mirror.py and
 tests/test_gpu_trace.py cover it through whole floods."""
 import time
 
