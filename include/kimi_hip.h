@@ -437,6 +437,23 @@ int kh_edt_graph_cells(const void* labels, int label_bytes, const uint32_t* grap
                        int black_border, uint8_t* cells, void* stream);
 int kh_edt_graph_sample(const float* fine, int64_t sx, int64_t sy, int64_t sz, float* out, void* stream);
 
+/* ---- the graph itself: cc3d.voxel_connectivity_graph(labels, connectivity), which the reference's docstring names as the source of
+ * skeletonize's voxel_graph (kimimaro/intake.py:113-117), extended by a list of label pairs (csrc/graph.hip).
+ * PARITY UNPINNED: cc3d's source is absent from the reference tree; the word is DEFINED here.
+ * graph[v] (u32 per voxel, F order) in cc3d's bit layout -- the inverse of kh_apply_voxel_graph's reading: bit 0 +x, 1 -x, 2 +y,
+ * 3 -y, 4 +z, 5 -z, 6..9 the xy edges, 10..13 the edges towards +z, 14..17 towards -z, 18..21 the +z corners, 22..25 the -z ones.
+ * The bit of a step is set iff (1) the step is one of the `connectivity` neighbours: 6 = bits 0..5, 18 = bits 0..17, 26 = all;
+ * (2) the neighbour lies inside the array; (3) the two label values a, b are equal -- background included, 0 == 0 -- or the
+ * unordered pair {a, b} is a row of `pairs`.  Bits 26..31 are clear.
+ * labels: 1, 2, 4 or 8 bytes each, compared at full width as bit patterns.
+ * pairs: npairs rows of two u64 (lo, hi), lo < hi, neither 0, sorted lexicographically, unique; NULL or npairs == 0: none.  The
+ * relation is NOT transitive: {a, b} and {b, c} do not connect a to c.  Up to KH_GRAPH_LDS_PAIRS rows are searched in LDS, more in
+ * global memory.  sx*sy*sz < 2^32, every extent and npairs < 2^31.  KH_EINVAL for another connectivity or label_bytes, a null
+ * pointer, a non-positive extent.                                                                                                 */
+#define KH_GRAPH_LDS_PAIRS 2048
+int kh_voxel_graph(const void* labels, int label_bytes, int64_t sx, int64_t sy, int64_t sz, int connectivity,
+                   const uint64_t* pairs, int64_t npairs, uint32_t* graph, void* stream);
+
 /* ---- f3: binary hole filling, replaces fill_voids.fill(img, in_place=True, return_fill_count=True) as
  * called at kimimaro/trace.py:109 (third-party, source absent): a background voxel (mask == 0) stays
  * background iff a 6-connected background path joins it to a face of the array.  mask/out: u8 [nvox]

@@ -29,6 +29,7 @@ SYMBOLS = [
     "kh_region_table_box", "kh_region_seam_pairs", "kh_region_apply_box",
     "kh_part_gaps", "kh_part_clusters", "kh_host_join_plan",
     "kh_heap_script", "kh_heap_flood",
+    "kh_voxel_graph",
 ]
 
 
@@ -68,6 +69,7 @@ TRACE_BIG_LDS_HEAP, TRACE_VOXEL_GRAPH, TRACE_SCRATCH_POOL, TRACE_FUSED_EDF = 64,
 HOLES_PROCESSED, HOLES_FILLED, HOLES_KILLED = 1, 2, 4    # KH_HOLES_*: the label states of kh_host_resolve_holes
 BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of kh_geodesic_relax / kh_feature_relax
 NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
+GRAPH_LDS_PAIRS = 2048           # KH_GRAPH_LDS_PAIRS: kh_voxel_graph searches a longer pair table in global memory
 
 
 def np_ptr(a):
@@ -204,6 +206,7 @@ def lib():
     L.kh_heap_script.argtypes = [ci, vp, i64, vp, i64, C.c_uint32, vp, i64, vp, i64, vp, vp]
     L.kh_heap_flood.argtypes = [ci, ci, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, i64, f32, f32, C.c_uint32, C.c_uint32,
                                 vp, i64, C.c_uint32, vp, vp, vp]
+    L.kh_voxel_graph.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",

@@ -6,6 +6,7 @@ that.  Each piece has its one owner here:
     _slices, _load_box                 a box of a dataset or a store as a host array, optionally checked against the shape asked for
     _store_box                         its writing counterpart: a host box into a dataset or a store
     store_like                         a store of the dataset's shape and one dtype: the caller's, checked, or a Fortran numpy array
+    clip_graph, GRAPH_STEP_OF_BIT      a box of a voxel connectivity graph without the bits that leave it; the word's layout
     label_table                        the skeletons' labels, their sorted table and each label's place in it
     upload_labels                      a host box of labels -> the device labels the kernels read, and the word of every table entry
     count_core, count_core_device      voxels per label of the table in a core, on the host and on the device
@@ -85,6 +86,36 @@ def store_like(given, shape, dtype, name, spelled=None, zeros=False):
         raise ValueError("{}: {} of shape {}. Got: {} of shape {}".format(name, spelled or np.dtype(dtype).name, shape, store.dtype,
                                                                           tuple(store.shape)))
     return store
+
+
+# cc3d's voxel-connectivity word listed by bit (the layout csrc/common.h reads: graph_to_directions / graph_bit_direction): bit b of a
+# voxel's word allows the step GRAPH_STEP_OF_BIT[b] away from it
+GRAPH_STEP_OF_BIT = (
+    (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (0, 0, -1),
+    (1, 1, 0), (-1, 1, 0), (1, -1, 0), (-1, -1, 0),
+    (1, 0, 1), (-1, 0, 1), (0, 1, 1), (0, -1, 1),
+    (1, 0, -1), (-1, 0, -1), (0, 1, -1), (0, -1, -1),
+    (1, 1, 1), (-1, 1, 1), (1, -1, 1), (-1, -1, 1),
+    (1, 1, -1), (-1, 1, -1), (1, -1, -1), (-1, -1, -1),
+)
+
+
+def graph_side_bits(axis, sign):
+    """the bits of a voxel-connectivity word whose step goes towards `sign` (-1 / +1) along `axis`"""
+    return sum(1 << b for b, step in enumerate(GRAPH_STEP_OF_BIT) if step[axis] == sign)
+
+
+def clip_graph(box):
+    """a box cut out of a dataset's voxel connectivity graph (three axes, _load_box) -> a Fortran-ordered uint32 copy with every bit
+    that leaves the box cleared, on its six face planes: the graph of the box ALONE.  skeletonize reads such bits:
+    the transform of a box that holds one value everywhere (black_border) asks the last voxel of an axis for its +x / +y / +z bit."""
+    out = np.array(box, dtype=np.uint32, order="F")
+    for axis in range(3):
+        low, high = [slice(None)] * 3, [slice(None)] * 3
+        low[axis], high[axis] = slice(0, 1), slice(out.shape[axis] - 1, out.shape[axis])
+        out[tuple(low)] &= np.uint32(~graph_side_bits(axis, -1) & 0xFFFFFFFF)
+        out[tuple(high)] &= np.uint32(~graph_side_bits(axis, 1) & 0xFFFFFFFF)
+    return out
 
 
 def label_table(skeletons, is_bool, span=None):

@@ -71,6 +71,13 @@ __host__ __device__ inline uint32_t graph_to_directions(uint32_t gw) {
   return m;
 }
 
+// the inverse table: the direction (dir_delta's index) whose step bit b of a voxel_connectivity_graph word allows -- bit 0 +x, 1 -x,
+// 2 +y, 3 -y, 4 +z, 5 -z, 6..9 the xy edges, 10..13 the edges towards +z, 14..17 towards -z, 18..21 the +z corners, 22..25 the -z ones
+__host__ __device__ constexpr inline int graph_bit_direction(int b) {
+  constexpr int8_t DIR[26] = {1, 0, 3, 2, 5, 4, 9, 7, 8, 6, 17, 15, 13, 11, 16, 14, 12, 10, 25, 24, 23, 21, 22, 20, 19, 18};
+  return DIR[b];
+}
+
 struct Geometry {
   int32_t sx, sy, sz;
   int32_t sxy;          // sx*sy (volumes are < 2^32 voxels, slices < 2^31)

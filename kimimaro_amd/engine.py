@@ -136,7 +136,15 @@ class Engine:
 
     def graph_to_device(self, voxel_graph, shape):
         """a voxel connectivity graph given on the host (cc3d's bit layout; fewer than three axes get trailing ones) -> u32 device
-        volume in Fortran order.  It must have the shape of the labels."""
+        volume in Fortran order.  It must have the shape of the labels.  A flat u32 / i32 tensor on this engine's device with the
+        volume's number of words (what voxel_graph returns) is taken as it is."""
+        t = self.torch
+        if isinstance(voxel_graph, t.Tensor):
+            words = int(shape[0]) * int(shape[1]) * int(shape[2])
+            if (voxel_graph.device != self.device or voxel_graph.ndim != 1 or voxel_graph.numel() != words
+                    or voxel_graph.dtype not in (t.int32, getattr(t, "uint32", t.int32)) or not voxel_graph.is_contiguous()):
+                raise ValueError("voxel_graph must have the shape of the labels")
+            return voxel_graph.view(t.int32)
         vg = as_3d(voxel_graph)
         if tuple(vg.shape) != tuple(shape):
             raise ValueError("voxel_graph must have the shape of the labels")
@@ -250,6 +258,18 @@ class Engine:
             d_cc.kh_u16 = d_cc16      # the u16 copy of the ids serves every later sweep (narrow()); it lives as long as this object
         rep = d_rep[: ncomp + 1].cpu().numpy().view(np.uint32)
         return d_cc, ncomp, rep
+
+    def voxel_graph(self, d_lab, itemsize, shape, connectivity=26, d_pairs=None):
+        """kh_voxel_graph (csrc/graph.hip) on a label volume resident in HBM: the voxel connectivity graph, a flat u32
+        device volume (int32 words) in Fortran order -- the form ccl_device, edt_graph and the searches take as d_graph.
+        itemsize: 1, 2, 4 or 8 bytes per label.  d_pairs: None, or a flat int64 device tensor of the pair table's rows (lo, hi) as
+        the kernel wants them: lo < hi, neither 0, sorted, unique (ops.merge_pairs makes them)."""
+        sx, sy, sz = (int(v) for v in shape)
+        d_graph = self.empty(sx * sy * sz, self.torch.int32)
+        npairs = 0 if d_pairs is None else int(d_pairs.numel()) // 2
+        _abi.check(self.lib.kh_voxel_graph(self.ptr(d_lab), int(itemsize), sx, sy, sz, int(connectivity),
+                                           self.optr(d_pairs if npairs else None), npairs, self.ptr(d_graph), self.stream()))
+        return d_graph
 
     def narrow(self, d_cc):
         """(device label volume, bytes per label) to sweep over: the u16 copy kh_ccl26 made of `d_cc` when it carries one, else

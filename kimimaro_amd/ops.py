@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _abi, feature, points, section
 from .engine import Engine
-from .volume import as_3d, coords_of, linear_index
+from .volume import DimensionError, _device_labels, as_3d, coords_of, linear_index
 
 _engine = None
 
@@ -42,6 +42,65 @@ def edt(labels, anisotropy=(1, 1, 1), black_border=False, parallel=1, voxel_grap
         return out.cpu().numpy().reshape(lab.shape, order="F").reshape(shape0, order="F")
     out = eng.edt(eng.to_device(lab), lab.dtype.itemsize, lab.shape, an, black_border, ndim=ndim)
     return out.cpu().numpy().reshape(lab.shape, order="F").reshape(shape0, order="F")
+
+
+def merge_pairs(merges, span, itemsize):
+    """`merges` of voxel_connectivity_graph -> the pair table kh_voxel_graph reads: uint64 [m, 2], each row (lo, hi) the words a
+    volume of `itemsize` bytes per label whose dtype holds `span` = (smallest, largest) stores for the two labels (intake._label_word),
+    lo < hi, rows sorted lexicographically, unique.  A pair that names 0 or one value twice is dropped; order and duplicates of the
+    input do not matter.  None and an empty list: no rows.  ValueError for anything but an (m, 2) array-like of integers and for a
+    value the dtype cannot hold.  numpy only."""
+    none = np.zeros((0, 2), dtype=np.uint64)
+    if merges is None:
+        return none
+    arr = np.asarray(merges)
+    if arr.size == 0 and arr.ndim <= 2:
+        return none
+    if arr.ndim != 2 or arr.shape[1] != 2:
+        raise ValueError("merges must be an (m, 2) array of label values. Got shape: {}".format(arr.shape))
+    if arr.dtype.kind not in "iub":
+        raise ValueError("merges must be integers. Got: {}".format(arr.dtype))
+    if int(arr.min()) < span[0] or int(arr.max()) > span[1]:
+        raise ValueError("merges name a value outside the labels' range {}..{}".format(span[0], span[1]))
+    if arr.dtype.kind == "u":
+        words = arr.astype(np.uint64)
+    else:
+        words = arr.astype(np.int64).view(np.uint64) & np.uint64((1 << (8 * itemsize)) - 1)     # (two's complement: value mod 2^bits)
+    words = np.sort(words, axis=1)
+    words = words[(words[:, 0] != 0) & (words[:, 0] != words[:, 1])]
+    return np.unique(words, axis=0) if words.shape[0] else none
+
+
+def pairs_to_device(eng, pairs):
+    """merge_pairs' table -> the flat int64 device tensor Engine.voxel_graph takes, None for an empty table"""
+    if not pairs.shape[0]:
+        return None
+    return eng.torch.from_numpy(np.ascontiguousarray(pairs).reshape(-1).view(np.int64)).to(eng.device)
+
+
+def voxel_connectivity_graph(labels, connectivity=26, merges=None):
+    """cc3d.voxel_connectivity_graph(labels, connectivity), the source of skeletonize's voxel_graph= that the reference's docstring
+    names (kimimaro/intake.py:113-117), on the MI355X (kh_voxel_graph; cc3d is absent from the reference tree: PARITY UNPINNED, the
+    word is DEFINED in DESIGN.md 3.21).  Returns a uint32 array of the labels' shape, Fortran ordered, in cc3d's bit layout: the bit
+    of a step is set iff the step is one of the `connectivity` (6, 18 or 26) neighbours, the neighbour lies inside the array and the
+    two labels are equal (background included) or listed together in `merges`.
+    labels: a 2-D or 3-D integer or bool numpy array of any order, or a tensor on the GPU; compared at full width.
+    merges: None, or an (m, 2) integer array-like of label values that belong together although they differ (the supervoxels of an
+      agglomerated segmentation).  NOT transitive: (a, b) and (b, c) do not connect a to c.  A pair that names 0 or a value twice is
+      dropped.  ValueError for another shape and for a value the labels' dtype cannot hold; so for another connectivity."""
+    if connectivity not in (6, 18, 26):
+        raise ValueError("connectivity must be 6, 18 or 26. Got: {}".format(connectivity))
+    if not hasattr(labels, "shape"):
+        labels = np.asarray(labels)
+    if len(labels.shape) not in (2, 3):
+        raise DimensionError("voxel_connectivity_graph needs labels of two or three axes. Got: {}".format(tuple(labels.shape)))
+    eng = engine()
+    d_lab, itemsize, is_bool, shape, shape0, span = _device_labels(eng, labels)
+    pairs = merge_pairs(merges, (0, 1) if is_bool else span, itemsize)
+    if d_lab.numel() == 0:
+        return np.zeros(shape0, dtype=np.uint32, order="F")
+    d_graph = eng.voxel_graph(d_lab, itemsize, shape, connectivity, pairs_to_device(eng, pairs))
+    return d_graph.cpu().numpy().view(np.uint32).reshape(shape, order="F").reshape(shape0, order="F")
 
 
 def roll_invalidation_cube(labels, DBF, path, scale, const, anisotropy=(1, 1, 1), invalid_vertices={}):

@@ -9,6 +9,9 @@
     postprocess_many(skeletons, dust_threshold=1500, tick_threshold=3000)
     skeletonize_chunked(dataset, chunk_shape, ...)                      a dataset in chunks to whole skeletons,
     place_fragment                                                      which composes postprocess_many with every box driver
+    voxel_connectivity_graph_chunked(dataset, chunk_shape, out, ...)    the voxel graph of a dataset, box by box
+    skeletonize_graph_chunked(dataset, chunk_shape, voxel_graph= | supervoxels=, merges=, ...)
+                                                                        skeletonize_chunked with a voxel graph for every box
 
 What else is done to a dataset in boxes lives in kimimaro_amd.boxes and the four driver modules on it, below this one, and is
 imported here, so that every name stays reachable as kimimaro_amd.post.NAME (also what only a moved function used):
@@ -19,6 +22,9 @@ imported here, so that every name stays reachable as kimimaro_amd.post.NAME (als
     section_boxes   the sections: cross_sectional_area_chunked, cross_sectional_area_filled_chunked, XS_CLIPPED
     segment_boxes   the segments: oversegment_chunked, shell_diff, DIRECTIONS
     point_boxes     the point queries: synapses_to_targets_chunked
+
+The voxel graph of a dataset in boxes lives here, next to the driver it feeds: voxel_connectivity_graph_chunked, and
+skeletonize_graph_chunked, which calls skeletonize_chunked through its _box_kwargs hook.
 
 Host code on graphs of 10^2..10^5 nodes: the reference is Python here and so are the single-skeleton
 functions; nothing in them touches the GPU path.  The two *_many functions do: the nearest pairs between all parts of all groups
@@ -41,9 +47,9 @@ from collections import defaultdict
 import numpy as np
 
 from . import _abi, intake, ops, points
-from .boxes import _load_box, axes, count_labels, label_type, route_targets
+from .boxes import _load_box, _store_box, axes, clip_graph, count_labels, down, label_type, route_targets, store_like
 from .lanes import Lanes, lanes_for
-from .plan import box_distance_bounds, chunk_grid, nearest_first  # noqa: F401
+from .plan import box_distance_bounds, chunk_grid, halo_boxes, nearest_first  # noqa: F401
 from .point_boxes import synapses_to_targets_chunked
 from .region_boxes import RegionGraph, _merge_regions, fill_all_holes_chunked, hole_lists, region_graph_chunked  # noqa: F401
 from .section_boxes import XS_CLIPPED, cross_sectional_area_chunked, cross_sectional_area_filled_chunked  # noqa: F401
@@ -312,8 +318,8 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
                         dust_threshold=1000, dust_global=False, post_dust_threshold=1500.0, tick_threshold=3000.0, merge=True,
                         fix_branching=True, fix_borders=True, fill_holes=False, fix_avocados=False, extra_targets_before=[],
                         extra_targets_after=[], progress=False, lanes=None, width=None, timings=None, _skeletonize=None,
-                        _postprocess=None, cross_sectional_area=None, fill_holes_global=False, filled_store=None, region_store=None,
-                        _fill=None, synapses=None, _synapse_targets=None):
+                        _postprocess=None, _box_kwargs=None, cross_sectional_area=None, fill_holes_global=False, filled_store=None,
+                        region_store=None, _fill=None, synapses=None, _synapse_targets=None):
     """A dataset in chunks to whole skeletons, {label: Skeleton} in ascending label order: what igneous does around
     kimimaro.skeletonize and kimimaro.postprocess, in one call.
 
@@ -353,6 +359,8 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
       (of the placed fragments); with fill_holes_global also fill_s and filled (the fill count).
     _fill replaces fill_all_holes_chunked, _synapse_targets replaces synapses_to_targets_chunked (the host-logic tests hand them
       their hooks).
+    _box_kwargs(eng, k, box_lo, box_hi) -> dict: further keyword arguments for the skeletonize call of box k, made by the lane that
+      takes the box (eng: its engine; None under _skeletonize) -- how skeletonize_graph_chunked hands every box its voxel_graph.
     _skeletonize(labels, **kwargs) -> {label: Skeleton} runs the boxes one after the other in place of the lanes,
     _postprocess(skeletons, dust_threshold, tick_threshold) -> list replaces postprocess_many: with both, nothing here touches the GPU
       (the host-logic tests run the whole driver on the CPU oracle).  Without them there is no CPU fallback."""
@@ -391,7 +399,7 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
             kept &= wanted
     count_s = time.perf_counter() - t0
 
-    def one(k, run):
+    def one(k, run, eng=None):
         labels = _load_box(dataset, grid.box_lo[k], grid.box_hi[k])
         ids, dust = object_ids, dust_threshold
         if kept is not None:
@@ -399,9 +407,10 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
             dust = 0
             if not ids:
                 return None
+        more = {} if _box_kwargs is None else _box_kwargs(eng, k, grid.box_lo[k], grid.box_hi[k])
         return run(labels, teasar_params=params, anisotropy=anisotropy, object_ids=ids, dust_threshold=dust, progress=False,
                    fix_branching=fix_branching, fix_borders=fix_borders, fill_holes=fill_holes, fix_avocados=fix_avocados,
-                   extra_targets_before=before[k], extra_targets_after=after[k])
+                   extra_targets_before=before[k], extra_targets_after=after[k], **more)
 
     t0 = time.perf_counter()
     if _skeletonize is not None:
@@ -415,7 +424,7 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
             lanes = Lanes(max(1, min(n, int(width))))
 
         def job(eng, k):
-            return one(k, lambda labels, **kw: intake.skeletonize(labels, _engine=eng, **kw))
+            return one(k, lambda labels, **kw: intake.skeletonize(labels, _engine=eng, **kw), eng)
 
         try:
             results = [res for _, res in lanes.run(job, n)]
@@ -455,6 +464,124 @@ def skeletonize_chunked(dataset, chunk_shape=(512, 512, 512), teasar_params=None
     if cross_sectional_area is not None:
         cross_sectional_area_chunked(dataset, out, **dict({"anisotropy": anisotropy}, **cross_sectional_area))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+def voxel_connectivity_graph_chunked(dataset, chunk_shape=(512, 512, 512), out=None, connectivity=26, merges=None, stats=None):
+    """voxel_connectivity_graph for a dataset that is never resident as a whole: DEFINED as what
+    voxel_connectivity_graph(dataset, connectivity, merges) returns for the whole dataset, word for word.
+
+    The cores of plan.halo_boxes(shape, chunk_shape, 1) partition the dataset; every core is loaded with one voxel around it (clamped
+    to the dataset), goes through kh_voxel_graph, and the words of the core are written to `out`: a word needs the 26 neighbours of
+    its voxel and nothing else.
+    dataset: numpy of any order, an np.memmap, a tensor on the GPU, or any object with .shape and slicing over a tuple of slices; two
+      or three axes, integers or bool.  It may hold 2^32 voxels or more: only a box has to stay below that.
+    out: an array-like of the dataset's shape and dtype uint32, written by slices; default: a Fortran-ordered numpy array in host
+      memory, 4 bytes per voxel of the dataset.  It is returned.
+    connectivity, merges: as voxel_connectivity_graph.
+    stats (a dict) receives cores, voxels_loaded, kernel_ms (HIP events around the kernel), load_s and store_s (seconds).
+    No CPU fallback: HipUnavailableError without the library or an MI355X."""
+    name = "voxel_connectivity_graph_chunked"
+    if connectivity not in (6, 18, 26):
+        raise ValueError("connectivity must be 6, 18 or 26. Got: {}".format(connectivity))
+    shape0, _, _ = axes(dataset, name)
+    core_lo, core_hi, box_lo, box_hi = halo_boxes(shape0, chunk_shape, 1)
+    extents = box_hi - box_lo
+    largest = tuple(int(v) for v in extents[int(np.argmax(np.prod(extents, axis=1)))])
+    if largest[0] * largest[1] * largest[2] >= 2 ** 32:
+        raise ValueError("{}: a box of {} voxels does not fit the 32-bit indices of a volume".format(name, largest))
+    eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
+    dtype, _, span = label_type(dataset)
+    d_pairs = ops.pairs_to_device(eng, ops.merge_pairs(merges, span, dtype.itemsize))
+    out = store_like(out, shape0, np.uint32, name)
+    events = []
+    loaded, load_s, store_s = 0, 0.0, 0.0
+    for k in range(int(core_lo.shape[0])):
+        t0 = time.perf_counter()
+        box = _load_box(dataset, box_lo[k], box_hi[k], name)
+        load_s += time.perf_counter() - t0
+        loaded += int(box.size)
+        d_box, itemsize, _, extent, _, _ = _device_labels(eng, box)
+        start, end = (eng.torch.cuda.Event(enable_timing=True) for _ in range(2))
+        start.record()
+        d_graph = eng.voxel_graph(d_box, itemsize, extent, connectivity, d_pairs)
+        end.record()
+        events.append((start, end))
+        inner = tuple(slice(int(a - b), int(c - b)) for a, b, c in zip(core_lo[k], box_lo[k], core_hi[k]))
+        core = down(d_graph, extent, inner).view(np.uint32)
+        t0 = time.perf_counter()
+        _store_box(out, core_lo[k], core_hi[k], core)
+        store_s += time.perf_counter() - t0
+        del d_box, d_graph
+    if stats is not None:
+        eng.sync_stream()
+        stats.update(cores=int(core_lo.shape[0]), voxels_loaded=loaded, kernel_ms=sum(a.elapsed_time(b) for a, b in events),
+                     load_s=load_s, store_s=store_s)
+    return out
+
+
+def skeletonize_graph_chunked(dataset, chunk_shape=(512, 512, 512), voxel_graph=None, supervoxels=None, merges=None, teasar_params=None,
+                              anisotropy=(1, 1, 1), object_ids=None, dust_threshold=1000, dust_global=False, post_dust_threshold=1500.0,
+                              tick_threshold=3000.0, merge=True, fix_branching=True, fix_borders=True, fill_holes=False,
+                              fix_avocados=False, extra_targets_before=[], extra_targets_after=[], progress=False, lanes=None,
+                              width=None, timings=None, _skeletonize=None, _postprocess=None, cross_sectional_area=None, synapses=None,
+                              _synapse_targets=None, _graph_of=None):
+    """skeletonize_chunked with a voxel connectivity graph: DEFINED as the composition of DESIGN.md 3.15 with every
+    box traced by skeletonize(box, voxel_graph=G_box, ...).  Exactly one of
+
+    voxel_graph: the graph of the dataset, an array-like of the dataset's shape read by slices (uint32, cc3d's bit layout; what
+      voxel_connectivity_graph_chunked writes, walls added by the caller included).  G_box = the slice of a box with every bit that
+      leaves the box cleared (boxes.clip_graph): skeletonize reads such bits of a box that holds one value everywhere;
+    supervoxels: a finer segmentation of the dataset, an array-like of its shape, with
+    merges: the (m, 2) pairs of supervoxel values that belong together (NOT transitive; ops.voxel_connectivity_graph).  G_box =
+      voxel_connectivity_graph(supervoxel box, 26, merges), built on the device by the lane that takes the box, from the box alone:
+      no halo, no 4 B per voxel store.  A supervoxel boundary that `merges` does not list is a wall -- the self-touches (autapses)
+      of an agglomerated label stay apart.
+
+    Cleared of the leaving bits, both are the same function of the box: supervoxels=S, merges=M gives what
+    voxel_graph=voxel_connectivity_graph_chunked(S, merges=M) gives.  Every other keyword is skeletonize_chunked's and means the
+    same; fill_holes_global, filled_store, region_store and _fill are not accepted (a graph of the original voxels does not
+    describe a filled dataset), and fix_avocados=True is a NotImplementedError before anything is loaded, as in skeletonize.
+    ValueError: both or neither of voxel_graph / supervoxels, merges without supervoxels, one of them of another shape than the
+    dataset.  _graph_of(box, merges=merges) -> uint32 graph replaces the device builder (the host-logic tests run the whole driver
+    on the CPU oracle); without the hooks there is no CPU fallback."""
+    name = "skeletonize_graph_chunked"
+    if fix_avocados:
+        raise NotImplementedError("{}(fix_avocados=True): the avocado pass re-labels components, which a graph of the ORIGINAL voxels "
+                                  "does not describe".format(name))
+    if (voxel_graph is None) == (supervoxels is None):
+        raise ValueError("{}: exactly one of voxel_graph and supervoxels".format(name))
+    if merges is not None and supervoxels is None:
+        raise ValueError("{}: merges belongs to supervoxels".format(name))
+    source = voxel_graph if voxel_graph is not None else supervoxels
+    if tuple(int(v) for v in source.shape) != tuple(int(v) for v in dataset.shape):
+        raise ValueError("{}: {} of shape {} for a dataset of shape {}".format(name, "voxel_graph" if voxel_graph is not None else "supervoxels",
+                                                                               tuple(source.shape), tuple(dataset.shape)))
+    pairs = None
+    if supervoxels is not None and _graph_of is None:
+        ops.engine()                                     # raises HipUnavailableError without the library or a gfx950 device
+        dtype, _, span = label_type(supervoxels)
+        pairs = ops.merge_pairs(merges, span, dtype.itemsize)
+
+    def box_kwargs(eng, k, lo, hi):
+        box = _load_box(source, lo, hi, name)
+        if voxel_graph is not None:
+            return {"voxel_graph": clip_graph(box)}
+        if _graph_of is not None:
+            return {"voxel_graph": _graph_of(box, merges=merges)}
+        own = eng if eng is not None else ops.engine()
+        d_box, itemsize, _, extent, _, _ = _device_labels(own, box)
+        d_graph = own.voxel_graph(d_box, itemsize, extent, 26, ops.pairs_to_device(own, pairs))
+        # (a lane's skeletonize takes the device words as they are; a caller's _skeletonize gets a host array)
+        return {"voxel_graph": d_graph if eng is not None else down(d_graph, extent).view(np.uint32)}
+
+    return skeletonize_chunked(dataset, chunk_shape, teasar_params=teasar_params, anisotropy=anisotropy, object_ids=object_ids,
+                               dust_threshold=dust_threshold, dust_global=dust_global, post_dust_threshold=post_dust_threshold,
+                               tick_threshold=tick_threshold, merge=merge, fix_branching=fix_branching, fix_borders=fix_borders,
+                               fill_holes=fill_holes, fix_avocados=False, extra_targets_before=extra_targets_before,
+                               extra_targets_after=extra_targets_after, progress=progress, lanes=lanes, width=width, timings=timings,
+                               _skeletonize=_skeletonize, _postprocess=_postprocess, cross_sectional_area=cross_sectional_area,
+                               synapses=synapses, _synapse_targets=_synapse_targets, _box_kwargs=box_kwargs)
 
 
 # ---------------------------------------------------------------------------------------------------------------
