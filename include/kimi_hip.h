@@ -795,6 +795,38 @@ int kh_part_clusters(const float* part_box, const uint32_t* group_start, const d
 int64_t kh_host_join_plan(int64_t nparts, const uint32_t* part_size, const uint64_t* rec_d2, const uint32_t* rec_idx,
                           const float* radii, double radius, int restrict_by_radius, uint32_t* edges);
 
+/* ---- row f4 on the device: the skeletons of a call packed back to back, "the forest"  ------------------------
+ * replaces: the Python loops over the vertices of one skeleton at a time in Skeleton.components, remove_dust, remove_loops and
+ * remove_ticks (kimimaro/post.py:222-362).  Vertices and edges of all skeletons are numbered call-wide; no edge joins two
+ * skeletons.  0 <= nverts, nedges < 2^31.  All three are asynchronous on `stream`, and the library allocates nothing.
+ *
+ * kh_forest_components: edges u32 [nedges,2] -> comp u32 [nverts], every word written: the smallest vertex connected to v (a
+ * vertex without an edge is its own).  comp doubles as the parent array of the union-find: three launches (identity, unions,
+ * flatten).  A function of the edge SET: the order of the rows does not matter.  A row that names a vertex >= nverts is skipped. */
+int kh_forest_components(const uint32_t* edges, int64_t nverts, int64_t nedges, uint32_t* comp, void* stream);
+
+/* kh_forest_measure: xyz f32 [nverts,3], edges, comp as above -> per component, AT ITS ROOT v = comp[v] (every other word 0):
+ * nv[v] its vertices, ne[v] its edges, cable[v] (f64) the sum of its edges' float32 lengths widened to f64, each length
+ * sqrtf(((dx*dx) + (dy*dy)) + (dz*dz)) of the float32 differences, correctly rounded, no FMA (Skeleton.cable_length's terms; the
+ * ORDER of the f64 sum is not fixed); and degree[v] for every vertex.  All four arrays have nverts words and all are written.
+ * Atomics: one 32-bit add per edge end (degree) and one add per run of equal roots among the 64 edges (vertices) of a wave.      */
+int kh_forest_measure(const float* xyz, const uint32_t* edges, const uint32_t* comp, int64_t nverts, int64_t nedges, double* cable,
+                      uint32_t* nv, uint32_t* ne, uint32_t* degree, void* stream);
+
+/* kh_forest_ticks: the tick removal of kimimaro/post.py:262-362 for every listed component at once, operation by operation
+ * (DESIGN.md 3.22 states it).  Adjacency as CSR: row_start u32 [nverts+1], nbr u32 [nslots] (nslots = 2 * edges), the neighbours of
+ * a vertex ascending.  A component is listed by its CRITICAL vertices (degree 1 or >= 3), ascending: crit u32 [ncrit], those of
+ * component c at [crit_start[c], crit_start[c+1]), crit_start u32 [ncomps+1].  Only trees with at least one vertex of degree >= 3
+ * may be listed (the caller checks ne == nv - 1); a component with fewer than two critical vertices is left alone.
+ * Output: alive u8 [nslots], every word written: 0 for both slots of every edge on a removed path, 1 elsewhere.
+ * Superedge lengths are accumulated in float32 from the end nearer the component's smallest terminal, outward, then widened; fused
+ * lengths are f64 sums; the next tick is the removable superedge of smallest (length, larger end, smaller end); `threshold` is f64.
+ * Scratch, sized by the caller: slot_scratch u32 [4*nslots], arity i32 [nverts], rec_scratch u32 [5*ncrit], rec_len f64 [ncrit],
+ * rec_flag u8 [ncrit].  One wave per component, no atomics.                                                                     */
+int kh_forest_ticks(const float* xyz, const uint32_t* row_start, const uint32_t* nbr, const uint32_t* crit, const uint32_t* crit_start,
+                    int64_t nverts, int64_t nslots, int64_t ncrit, int64_t ncomps, double threshold, uint32_t* slot_scratch,
+                    int32_t* arity, uint32_t* rec_scratch, double* rec_len, uint8_t* rec_flag, uint8_t* alive, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

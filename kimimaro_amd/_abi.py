@@ -30,6 +30,7 @@ SYMBOLS = [
     "kh_part_gaps", "kh_part_clusters", "kh_host_join_plan",
     "kh_heap_script", "kh_heap_flood",
     "kh_voxel_graph",
+    "kh_forest_components", "kh_forest_measure", "kh_forest_ticks",
 ]
 
 
@@ -207,6 +208,9 @@ def lib():
     L.kh_heap_flood.argtypes = [ci, ci, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, i64, f32, f32, C.c_uint32, C.c_uint32,
                                 vp, i64, C.c_uint32, vp, vp, vp]
     L.kh_voxel_graph.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp, vp]
+    L.kh_forest_components.argtypes = [vp, i64, i64, vp, vp]
+    L.kh_forest_measure.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
+    L.kh_forest_ticks.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         getattr(L, name)
         if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",

@@ -14,6 +14,7 @@
 // by (d2, other, own); every distance is evaluated once.  Keys are 128 bits: they are reduced in registers, across the wave with
 // shuffles, across the four waves through LDS, and each record is written once by one lane -- no global atomics.
 #include "common.h"
+#include "unionfind.h"
 
 #include <math.h>
 
@@ -181,39 +182,8 @@ __global__ __launch_bounds__(256) void part_gaps_kernel(const float* __restrict_
 }
 
 // ---- the broad phase: connected sets of near parts ----------------------------------------------------------------
-// A union-find whose parent array IS the output.  parent[x] <= x always: a root is hooked under a smaller root only, by one integer
-// CAS that succeeds only while it still is a root, so the trees never form a cycle and, once every near pair has been united, the
-// root of a tree is the smallest part of its connected set -- whatever order the unions arrived in.  A parent word only ever moves to
-// another ancestor of its node, so a reader that sees an older value still walks to the root.  These are the only global atomics of
-// this file: 32-bit integers, one successful CAS per true union, and no floating-point value goes through them.
-__device__ __forceinline__ uint32_t uf_load(const uint32_t* parent, uint32_t x) {
-  return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {      // with path halving
-  for (;;) {
-    const uint32_t p = uf_load(parent, x);
-    if (p == x) return x;
-    const uint32_t gp = uf_load(parent, p);
-    if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = gp;
-  }
-}
-
-__device__ __forceinline__ void uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-  for (;;) {
-    a = uf_find(parent, a);
-    b = uf_find(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      const uint32_t s = a;
-      a = b;
-      b = s;
-    }
-    if (atomicCAS(parent + a, a, b) == a) return;      // the larger root under the smaller; it was hooked meanwhile: walk on from both
-  }
-}
-
+// The union-find of unionfind.h, whose parent array IS the output.  Its CAS words are the only global atomics of this file: 32-bit
+// integers, one successful CAS per true union, and no floating-point value goes through them.
 __global__ __launch_bounds__(256) void part_clusters_init_kernel(uint32_t* __restrict__ cluster, uint32_t nparts) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p < nparts) cluster[p] = p;

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _abi, feature, points, section
+from . import _abi, feature, forest, points, section
 from .engine import Engine
 from .volume import DimensionError, _device_labels, as_3d, coords_of, linear_index
 
@@ -506,3 +506,11 @@ def component_clusters(parts, bound):
         return np.zeros(0, dtype=np.uint32)
     _, _, boxes = points.part_boxes(verts)
     return points.part_clusters(eng, boxes, [0, len(verts)], [bound * bound])
+
+
+def skeleton_component_labels(skeleton):
+    """The labelling components_many works from (kh_forest_components), for ONE skeleton: comp u32 [n] over the vertices
+    of skeleton.consolidate(), comp[v] = the smallest vertex connected to v.  The components of the skeleton, in the order
+    Skeleton.components() lists them, are the distinct values in ascending order."""
+    eng = engine()
+    return forest.labels(eng, forest.pack([skeleton.consolidate()]))

@@ -46,7 +46,7 @@ from collections import defaultdict
 
 import numpy as np
 
-from . import _abi, intake, ops, points
+from . import _abi, forest, intake, ops, points
 from .boxes import _load_box, _store_box, axes, clip_graph, count_labels, down, label_type, route_targets, store_like
 from .lanes import Lanes, lanes_for
 from .plan import box_distance_bounds, chunk_grid, halo_boxes, nearest_first  # noqa: F401
@@ -150,6 +150,15 @@ def join_parts(skeletons):
     return [p for p in parts if not p.empty()]
 
 
+def join_parts_many(groups):
+    """join_parts for every group, the components of ALL their skeletons from one components_many call.  A component
+    comes out of it consolidated -- vertices sorted and unique, edge rows sorted and unique, no vertex without an edge -- so the
+    consolidate() of join_parts would hand back the same arrays and is not repeated."""
+    groups = [[g] if isinstance(g, Skeleton) else list(g) for g in groups]
+    comps = iter(components_many([s for g in groups for s in g]))
+    return [[c for _ in g for c in next(comps) if not c.empty()] for g in groups]
+
+
 def join_plan(part_sizes, d2, idx, radii, radius, restrict_by_radius):
     """kh_host_join_plan (host C, no GPU needed; include/kimi_hip.h): the edges u32 [m, 2], in the numbering of the concatenated parts,
     that join_close_components adds to one group, from the table of nearest pairs (d2 f64 [n, n], idx u32 [n, n, 2]) of its parts."""
@@ -202,7 +211,7 @@ def lift_edges(edges, members, part_sizes):
     return (first[members[k]] + (edges - own[k])).astype(np.uint32).reshape(-1, 2)
 
 
-def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, timings=None, split=None):
+def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, timings=None, split=None, parts_from="device"):
     """join_close_components for many groups at once: each group is a Skeleton or a sequence of them, the result per
     group what join_close_components(group, radius, restrict_by_radius) returns -- Skeleton.simple_merge of its parts plus one edge
     per merge, consolidated.  The nearest pairs between the parts of ALL groups come from one kernel call (a few when their tables
@@ -217,15 +226,22 @@ def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, 
     None (default): only the groups of more than 8 192 parts, which have no table of their own; True: every group with a finite
     bound; False: none.  A set of more than 8 192 parts is a ValueError, and so is a group of that size that is not split (an
     infinite radius, or split=False).
-    timings (a dict): kernel_ms, copy_s, plan_s of the call; cluster_ms (HIP events around kh_part_clusters), clusters (the sets of
-    two or more parts that were joined on their own) and largest_cluster (parts in the largest set; 0 when nothing was split)."""
+    parts_from: "device" (default): the parts of all groups come from one components_many call (join_parts_many, DESIGN.md 3.22);
+    "host": from Skeleton.components() skeleton by skeleton (join_parts).  They are the same parts.
+    timings (a dict): kernel_ms, copy_s, plan_s of the call; parts_s, the seconds spent making the parts; cluster_ms (HIP events
+    around kh_part_clusters), clusters (the sets of two or more parts that were joined on their own) and largest_cluster (parts in the
+    largest set; 0 when nothing was split)."""
     if radius is None:
         radius = np.inf
     if radius <= 0:
         raise ValueError("radius must be greater than zero: " + str(radius))
     eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     groups = list(groups)
-    parts = [join_parts(g) for g in groups]
+    if parts_from not in ("device", "host"):
+        raise ValueError("parts_from must be 'device' or 'host': " + repr(parts_from))
+    t0 = time.perf_counter()
+    parts = join_parts_many(groups) if parts_from == "device" else [join_parts(g) for g in groups]
+    parts_s = time.perf_counter() - t0
     radius_of = [float(radius)] * len(groups)
     if restrict_by_radius:
         radius_of = [max(2 * max(float(np.max(p.radii)) for p in ps), 0) if ps else 0.0 for ps in parts]
@@ -269,24 +285,138 @@ def join_close_components_many(groups, radius=np.inf, restrict_by_radius=False, 
         out[g] = merged.consolidate(remove_disconnected_vertices=True)
     if timings is not None:
         timings["plan_s"] = timings.get("plan_s", 0.0) + time.perf_counter() - t0
+        timings["parts_s"] = timings.get("parts_s", 0.0) + parts_s
         timings["cluster_ms"] = timings.get("cluster_ms", 0.0) + cluster_ms.get("cluster_ms", 0.0)
         timings["clusters"] = timings.get("clusters", 0) + clusters
         timings["largest_cluster"] = max(timings.get("largest_cluster", 0), largest)
     return out
 
 
-def postprocess_many(skeletons, dust_threshold=1500.0, tick_threshold=3000.0):
-    """postprocess for many skeletons: dust and loops out per skeleton on the host, the join of ALL of them in one
-    join_close_components_many(restrict_by_radius=True) call, ticks out per skeleton on the host."""
+def components_many(skeletons):
+    """Skeleton.components() for every skeleton of the list, from one device labelling of all of them (kh_forest_components, DESIGN.md
+    3.22): per skeleton the list of its components, ordered by their smallest vertex, each with the arrays components() gives it.
+    No CPU fallback: HipUnavailableError without the library or an MI355X."""
+    eng = ops.engine()
+    packed = [forest.consolidated(s) for s in skeletons]
+    out = []
+    for part in forest.batches(packed):
+        f = forest.pack(packed[part])
+        out.extend(forest.unpack_components(f, forest.labels(eng, f)))
+    return out
+
+
+def remove_dust_many(skeletons, dust_threshold, stats=None):
+    """remove_dust(skeleton, dust_threshold) for every skeleton of the list; an empty skeleton, and every skeleton
+    under a zero threshold, comes back as the object it is.  The cable length of every component is summed on the device in another
+    order than numpy's float32 sum, so the device decides a component only when |cable - T| > cable * ne * 2^-23 -- twice the bound
+    (ne - 1) * 2^-24 on the relative error of a float32 sum of ne non-negative terms in any order, which also covers the order of
+    the device's own f64 sum -- and the host's cable_length() > T decides the others and every component of 2^20 edges or more.
+    stats (a dict): `components` and `dust_host_decided` are added to.  No CPU fallback."""
+    eng = ops.engine()
+    out = list(skeletons)
+    todo = [k for k, s in enumerate(out) if not (s.empty() or dust_threshold == 0)]
+    packed = [forest.consolidated(out[k]) for k in todo]
+    ncomp = nhost = 0
+    for part in forest.batches(packed):
+        f = forest.pack(packed[part])
+        m = forest.measure(eng, f)
+        g = forest.Groups(f, m.comp)
+        cable, ne = m.cable[g.root], m.ne[g.root].astype(np.float64)
+        keep = cable > dust_threshold
+        unsure = ~(np.abs(cable - dust_threshold) > cable * ne * 2.0 ** -23) | (ne >= forest.HOST_DUST_EDGES)
+        for k in np.flatnonzero(unsure & (ne > 0)).tolist():
+            keep[k] = forest.component_cable(f, g, k) > dust_threshold
+            nhost += 1
+        ncomp += int(np.count_nonzero(ne > 0))
+        for k, skel in zip(todo[part], forest.unpack_dust(f, g, keep & (ne > 0))):
+            out[k] = skel
+    if stats is not None:
+        stats["components"] = stats.get("components", 0) + ncomp
+        stats["dust_host_decided"] = stats.get("dust_host_decided", 0) + nhost
+    return out
+
+
+def _all_trees(f, m):
+    """per skeleton of the forest: it has edges and every component of it is a tree (ne == nv - 1, counted on the device)"""
+    roots = np.flatnonzero(m.nv)
+    cyclic = m.ne[roots].astype(np.int64) != m.nv[roots].astype(np.int64) - 1
+    bad = np.zeros(len(f.skeletons), dtype=bool)
+    bad[f.skeleton_of_vertex(roots[cyclic])] = True
+    return ~bad & (np.diff(f.estart) > 0)
+
+
+def remove_loops_many(skeletons, stats=None):
+    """remove_loops(skeleton) for every skeleton of the list.  Whether a component holds a cycle is counted on the
+    device; a skeleton of trees is returned as skeleton.consolidate(), which is what remove_loops makes of a forest (the skeleton
+    itself where it is consolidated already: forest.consolidated), and a skeleton
+    with a cyclic component goes through the host's remove_loops whole: the four cycle rules stay host code.  An empty skeleton comes
+    back as the object it is.  stats (a dict): `loops_host`, the skeletons that took the host path, is added to.  No CPU fallback."""
+    eng = ops.engine()
+    out = list(skeletons)
+    todo = [k for k, s in enumerate(out) if not s.empty()]
+    packed = [forest.consolidated(out[k]) for k in todo]
+    nhost = 0
+    for part in forest.batches(packed):
+        f = forest.pack(packed[part])
+        trees = _all_trees(f, forest.measure(eng, f))
+        for k, skel, ok in zip(todo[part], packed[part], trees.tolist()):
+            if not ok:
+                nhost += 1
+            out[k] = skel if ok else remove_loops(out[k])
+    if stats is not None:
+        stats["loops_host"] = stats.get("loops_host", 0) + nhost
+    return out
+
+
+def remove_ticks_many(skeletons, threshold):
+    """remove_ticks(skeleton, threshold) for every skeleton of the list, every tree of all of them in one kh_forest_ticks call
+    (DESIGN.md 3.22): consolidated, the vertices that lost all their edges kept.  An empty skeleton, and every skeleton under a zero
+    threshold, comes back as the object it is; a component with a cycle raises the ValueError of distance_graph.  No CPU fallback."""
+    eng = ops.engine()
+    out = list(skeletons)
+    todo = [k for k, s in enumerate(out) if not (s.empty() or threshold == 0)]
+    packed = [forest.consolidated(out[k]) for k in todo]
+    for part in forest.batches(packed):
+        f = forest.pack(packed[part])
+        m = forest.measure(eng, f)
+        trees = _all_trees(f, m)
+        for skel, ok in zip(packed[part], trees.tolist()):
+            if not ok and not skel.empty():
+                for c in skel.components():
+                    distance_graph(c)
+                raise ValueError("distance_graph: a component contains a cycle")
+        done = forest.unpack_ticks(f, forest.ticks(eng, f, m, threshold))
+        for k, skel, ok in zip(todo[part], done, trees.tolist()):
+            out[k] = skel if ok else remove_ticks(out[k], threshold)      # (without edges once consolidated: the host's answer)
+    return out
+
+
+def postprocess_many(skeletons, dust_threshold=1500.0, tick_threshold=3000.0, stages="device", stats=None):
+    """postprocess for many skeletons: dust and loops out, the join of ALL of them in one join_close_components_many(
+    restrict_by_radius=True) call, ticks out.
+    stages="device" (default): remove_dust_many, remove_loops_many and remove_ticks_many around the join, each one pass over all
+    skeletons; stats (a dict) is handed to them.  stages="host": the three per skeleton on the host.  The results
+    are equal: every *_many function is defined as what the host function returns."""
+    if stages not in ("device", "host"):
+        raise ValueError("stages must be 'device' or 'host': " + repr(stages))
     skeletons = list(skeletons)
     ops.engine()                                         # raises HipUnavailableError without the library or a gfx950 device
+    if stages == "device":
+        cleaned = remove_loops_many(remove_dust_many([s.consolidate(remove_disconnected_vertices=True) for s in skeletons],
+                                                     dust_threshold, stats=stats), stats=stats)
+        joined = remove_ticks_many(join_close_components_many(cleaned, restrict_by_radius=True), tick_threshold)
+        out = []
+        for skeleton, skel in zip(skeletons, joined):
+            skel.id = skeleton.id
+            out.append(skel.consolidate(remove_disconnected_vertices=True))
+        return out
     cleaned = []
     for skeleton in skeletons:
         skel = skeleton.consolidate(remove_disconnected_vertices=True)
         skel = remove_dust(skel, dust_threshold)
         cleaned.append(remove_loops(skel))
     out = []
-    for skeleton, skel in zip(skeletons, join_close_components_many(cleaned, restrict_by_radius=True)):
+    for skeleton, skel in zip(skeletons, join_close_components_many(cleaned, restrict_by_radius=True, parts_from="host")):
         skel = remove_ticks(skel, tick_threshold)
         skel.id = skeleton.id
         out.append(skel.consolidate(remove_disconnected_vertices=True))
