@@ -10,6 +10,8 @@
 // degrees; and for the sums per component ONE add per run of equal roots in a wave -- edges arrive sorted by their smaller vertex,
 // so the lanes of a wave mostly hold one component or a few -- never one per edge.  The order in which the runs of a component reach
 // its f64 sum is not fixed: remove_dust_many decides on the device only outside a band that covers every order.
+// (Where the sum stays below 2^30 times the power of two at or below the smallest length, every partial sum is an exact f64 and the
+// order cannot show: the tests pin the cable bit for bit on such inputs.)
 // kh_forest_ticks uses none: a component belongs to one wave.
 #include "common.h"
 #include "unionfind.h"

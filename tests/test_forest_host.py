@@ -245,3 +245,195 @@ def test_forest_sits_below_ops_and_post():
             names = [node.module] if isinstance(node, ast.ImportFrom) else [a.name for a in node.names]
             found.update(n.split(".")[1] for n in names if n and n.startswith("kimimaro_amd."))
     assert found == {"_abi", "skeleton"}
+
+
+# ---- the model's tables and the exact cable (tests/test_gpu_forest_calls.py holds the device to them) ------------------------------------
+FILL = 0xA5
+WORD = int(R.filled(1, np.uint32, FILL)[0])
+TABLE_CALLS = R.TABLE_CASES + ("tick_forest",)
+
+
+def survival(f, threshold):
+    """bool per edge row of the forest: the row is still an edge of post.remove_ticks(skeleton, threshold)"""
+    out = np.ones(f.nedges, dtype=bool)
+    for k, skel in enumerate(f.skeletons):
+        a, b = int(f.estart[k]), int(f.estart[k + 1])
+        if a == b or threshold == 0:                                          # (remove_ticks hands a skeleton back under a zero threshold)
+            continue
+        left = np.asarray(post.remove_ticks(skel, threshold).edges, dtype=np.int64).reshape(-1, 2)
+        mine = f.edges[a:b].astype(np.int64) - int(f.vstart[k])
+        out[a:b] = np.isin((mine[:, 0] << 32) | mine[:, 1], (left[:, 0] << 32) | left[:, 1])
+    return out
+
+
+@pytest.mark.parametrize("name", TABLE_CALLS)
+def test_tick_tables_alive_is_remove_ticks_survival(name):
+    f, m, thresholds = R.table_call(name)
+    assert thresholds[0] == 0.0 and thresholds[-1] == np.inf and len(thresholds) >= 3
+    removed = []
+    for threshold in thresholds:
+        T = R.tick_tables(f, m, threshold, fill=FILL)
+        both = np.argsort(slot_keys(T), kind="stable").reshape(-1, 2)         # the two slots of every edge
+        assert T.alive.dtype == np.uint8 and np.array_equal(T.alive[both[:, 0]], T.alive[both[:, 1]])
+        got = T.alive[T.upper] != 0
+        assert np.array_equal(got, survival(f, threshold)), threshold
+        assert np.array_equal(got, R.ticks(f, m, threshold))
+        removed.append(int(f.nedges - got.sum()))
+    assert removed[0] == 0 and removed == sorted(removed) and removed[-1] > 0     # a larger threshold goes on where a smaller one stops
+
+
+def slot_keys(T):
+    row = T.row.astype(np.int64)
+    own = np.repeat(np.arange(row.size - 1), np.diff(row))
+    nbr = T.nbr.astype(np.int64)
+    return (np.minimum(own, nbr) << 32) | np.maximum(own, nbr)
+
+
+def chain(row, nbr, c, s):
+    """the vertices from the critical vertex c through its slot s to the next critical vertex"""
+    path = [int(c), int(nbr[s])]
+    while row[path[-1] + 1] - row[path[-1]] == 2:
+        n0, n1 = int(nbr[row[path[-1]]]), int(nbr[row[path[-1]] + 1])
+        path.append(n1 if n0 == path[-2] else n0)
+    return path
+
+
+@pytest.mark.parametrize("name", TABLE_CALLS)
+def test_threshold_zero_leaves_the_orientation(name):
+    """the tables after a call with threshold 0, checked without the model's own loop: what an orientation of a contracted tree is"""
+    f, m, _ = R.table_call(name)
+    T = R.tick_tables(f, m, 0.0, fill=FILL)
+    row, nbr = T.row.astype(np.int64), T.nbr.astype(np.int64)
+    deg = np.diff(row)
+    own = np.repeat(np.arange(f.nverts), deg)
+    crit, start = T.crit.astype(np.int64), T.crit_start.astype(np.int64)
+    assert T.alive.all() and np.array_equal(T.arity, np.where(deg >= 3, deg, 0)) and T.arity.dtype == np.int32
+    assert [getattr(T, k).dtype for k in T.SLOT + T.RECORD] == [np.uint32, np.uint32, np.float32, np.uint32] + [np.uint32] * 5 + [np.float64, np.uint8]
+    # slots: written for the listed critical vertices and for no other
+    mine = np.zeros(f.nverts, dtype=bool)
+    mine[crit] = True
+    for table in T.SLOT:
+        words = getattr(T, table).view(np.uint32)
+        assert np.all(words[~mine[own]] == WORD) and (table == "len32" or np.all(words[mine[own]] != WORD)), table
+    slots = np.flatnonzero(mine[own])
+    twin, far = T.twin.astype(np.int64), T.far.astype(np.int64)
+    assert np.array_equal(twin[twin[slots]], slots) and np.array_equal(far[twin[slots]], own[slots]) and np.array_equal(own[twin[slots]], far[slots])
+    for s in slots.tolist():
+        path = chain(row, nbr, own[s], s)
+        assert path[-1] == far[s] and nbr[twin[s]] == path[-2]
+        assert float(T.len32[s]) == R.directed_sums(f.xyz[path])[0], s
+    assert start.size - 1 >= 1 and start[-1] == crit.size
+    for c in range(start.size - 1):
+        cs, ce = int(start[c]), int(start[c + 1])
+        assert T.tail[c] == ce
+        terminals = crit[cs:ce][deg[crit[cs:ce]] == 1]
+        queue = T.queue[cs:ce].astype(np.int64)
+        assert np.array_equal(np.sort(queue), crit[cs:ce]) and queue[0] == terminals.min()
+        assert T.sb[cs] == R.NONE and T.flag[cs] == 0
+        assert all(getattr(T, k)[cs:cs + 1].tobytes() == bytes([FILL]) * getattr(T, k).itemsize for k in ("ea", "eb", "sa", "len"))
+        # records cs + 1 .. ce - 1: one per critical vertex but the start, each the superedge through which its vertex was reached
+        i = np.arange(cs + 1, ce)
+        assert i.size == (ce - cs) - 1 and np.all(np.isin(T.flag[i], (R.LIVE, R.LIVE | R.REMOVABLE)))
+        ea, eb, sa, sb = (getattr(T, k)[i].astype(np.int64) for k in ("ea", "eb", "sa", "sb"))
+        assert np.array_equal(eb, queue[1:]) and np.array_equal(own[sa], ea) and np.array_equal(own[sb], eb)
+        assert np.array_equal(twin[sa], sb) and np.array_equal(T.rec[sa], i) and np.array_equal(T.rec[sb], i)
+        assert np.array_equal(T.len[i].view(np.uint64), T.len32[sa].astype(np.float64).view(np.uint64))
+        place = {int(v): k for k, v in enumerate(queue)}
+        assert all(place[int(a)] < k + 1 for k, a in enumerate(ea))            # the parent was queued before its child
+        assert np.array_equal(T.flag[i] == (R.LIVE | R.REMOVABLE), (deg[ea] == 1) | (deg[eb] == 1))
+
+
+def chunked_queue(T, c):
+    """the queue of listed component c as forest_ticks_kernel fills it: rounds of at most 64 entries, a lane per entry, every lane's
+    children placed behind the queue's end at the exclusive prefix sum of the lanes' child counts -- the lanes taken LAST FIRST here,
+    which must not matter"""
+    row = T.row.astype(np.int64)
+    cs, ce = int(T.crit_start[c]), int(T.crit_start[c + 1])
+    terminals = [int(v) for v in T.crit[cs:ce] if row[v + 1] - row[v] == 1]
+    queue, via = [min(terminals)], [R.NONE]
+    head = 0
+    while head < len(queue):
+        n = min(64, len(queue) - head)
+        cnt = np.array([row[queue[head + lane] + 1] - row[queue[head + lane]] - (via[head + lane] != R.NONE) for lane in range(n)])
+        pos = len(queue) + np.cumsum(cnt) - cnt
+        queue += [None] * int(cnt.sum())
+        via += [None] * int(cnt.sum())
+        for lane in reversed(range(n)):
+            u, p = queue[head + lane], int(pos[lane])
+            for s in range(row[u], row[u + 1]):
+                if s != via[head + lane]:
+                    queue[p], via[p] = int(T.far[s]), int(T.twin[s])
+                    p += 1
+        head += n
+    return queue
+
+
+def test_rounds_of_64_give_the_queue_of_the_fifo():
+    f, m, _ = R.table_call("wide_round")
+    T = R.tick_tables(f, m, 0.0, fill=FILL)
+    assert f.nverts == 281 and T.crit_start.tolist() == [0, 211]              # 140 leaves, 70 forks and the hub
+    queue = chunked_queue(T, 0)
+    assert queue == T.queue.tolist()
+    deg = np.diff(T.row.astype(np.int64))
+    assert deg[queue[2]] == 70 or deg[queue[3]] == 70                         # the hub is in the third round
+    assert [deg[v] for v in queue[4:73]] == [3] * 69                          # the fourth: 69 forks, lanes 0..63 and then 0..4
+
+
+# ---- the measures ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(R.measure_shapes()) + ["all"])
+def test_measure_shapes_have_an_exact_cable(name):
+    """the CPU side of tests/test_gpu_forest_calls.py's bit-for-bit cable: its condition holds, and the model's sum in edge order is
+    math.fsum's already"""
+    f, m, exact = R.measure_call(name)
+    by_root = R.lengths_by_root(f, m.comp)
+    assert sorted(by_root) == np.flatnonzero(m.ne).tolist() == np.flatnonzero(m.nv).tolist()
+    assert all(R.cable_is_exact(lengths) for lengths in by_root.values())
+    assert np.array_equal(exact.view(np.uint64), m.cable.view(np.uint64))
+    assert int(m.nv.sum()) == f.nverts and int(m.ne.sum()) == f.nedges and int(m.degree.sum()) == 2 * f.nedges
+
+
+def test_measure_shapes_reach_their_regimes():
+    for n in R.PATH_EDGES:
+        f, m, _ = R.measure_call("path_%d" % n)
+        assert f.nedges == n and m.nv[0] == n + 1 and m.ne[0] == n and not m.comp.any()
+        d = np.abs(np.diff(f.xyz.astype(np.float64), axis=0))
+        assert np.all((d > 0).sum(axis=0) >= n - 2)                           # all three axes move
+        sq = d * d
+        assert np.any(sq != sq.astype(np.float32))                            # and a square rounds in float32
+    f, m, _ = R.measure_call("pairs_5000")
+    assert f.nedges == 5000 == R.wave_runs(m.comp[f.edges[:, 0]]) == np.count_nonzero(m.nv) and np.all(m.nv[m.nv > 0] == 2)
+    f, m, _ = R.measure_call("braid_3x700")
+    assert f.nedges == 2097 == R.wave_runs(m.comp[f.edges[:, 0]]) and np.flatnonzero(m.nv).tolist() == [0, 1, 2]
+    assert m.nv[:3].tolist() == [700] * 3 and m.ne[:3].tolist() == [699] * 3
+    f, m, _ = R.measure_call("hub_5000")
+    assert m.degree[2500] == 5000 and m.degree[0] == 1 and not m.comp.any() and m.ne[0] == 5000
+    assert R.wave_runs(m.comp[f.edges[:, 0]]) == -(-5000 // 64)
+    f, m, _ = R.measure_call("ring_and_tree")
+    roots = np.flatnonzero(m.nv)
+    assert m.nv[roots].tolist() == [64, 40] and m.ne[roots].tolist() == [64, 39]
+    f, m, exact = R.measure_call("one_edge")
+    assert f.nedges == 1 and exact[0] == float(R.edge_lengths(f.xyz, f.edges)[0]) and exact[1] == 0
+    f, m, _ = R.measure_call("forests_300")
+    assert (f.nverts, f.nedges) == (16562, 15515)
+
+
+def test_cable_is_exact_is_a_condition_on_the_spread():
+    assert R.cable_is_exact([]) and R.cable_is_exact([1.0]) and R.cable_is_exact([1.0, 2.0 ** 29])
+    assert not R.cable_is_exact([1.0, 2.0 ** 30]) and not R.cable_is_exact([0.0, 1.0]) and not R.cable_is_exact([1.5, np.inf])
+    assert R.cable_is_exact([1.75] * 1000) and not R.cable_is_exact([1.0 + 2.0 ** -23] * 2 ** 20 + [2.0 ** 30])
+    # where it fails the order can matter: 2^30 + 1.5 + 1.5 from the left keeps both halves, from the right it does not
+    terms = [2.0 ** 53, 1.0, 1.0]
+    assert (terms[0] + terms[1]) + terms[2] != terms[0] + (terms[1] + terms[2])
+
+
+@pytest.mark.parametrize("name", R.TREE_SHAPES)
+def test_tree_shapes_take_no_host_path_in_the_statement(name):
+    skels = R.measure_shapes()[name]
+    f, m, _ = R.measure_call(name)
+    threshold = R.dust_threshold(f, m)
+    with R.host_engine():
+        stats = {}
+        got = post.remove_loops_many(skels, stats=stats)
+        assert stats["loops_host"] == 0 and all(R.same(a, s.consolidate()) for a, s in zip(got, skels))
+        got = post.remove_dust_many(skels, threshold, stats=stats)
+        assert stats["dust_host_decided"] == 0 and stats["components"] == np.count_nonzero(m.nv)
