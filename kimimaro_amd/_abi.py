@@ -1,4 +1,10 @@
-"""ctypes binding of libkimi_hip.so (include/kimi_hip.h).
+"""ctypes binding of libkimi_hip.so, derived from include/kimi_hip.h.
+
+The header is the one statement of the C ABI.  This module reads it once at import -- no library, no torch -- and takes from it
+the prototypes (``PROTOTYPES``, ``SYMBOLS``; ``lib()`` applies them to the CDLL), the ``KH_*`` constants and ``kh_label_t``
+(``LABEL_T``).  The readers are closed: a type or a value form they do not know raises, naming it, instead of defaulting.  They
+rely on the header's regular style: one prototype per ``;`` that begins its line with its return type, no function pointers
+or macros in signatures (tests/test_abi.py checks that every prototype is consumed).
 
 There is NO CPU fallback: if the library is missing, cannot be loaded, or no gfx950 device is
 visible, every compute entry point raises ``HipUnavailableError``.
@@ -7,31 +13,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # KIMI_HIP_LIB: developer knob -- another build of the same sources (e.g. -DKH_SWEEP_PROBE, kimimaro_amd/build.py)
 LIB_PATH = os.environ.get("KIMI_HIP_LIB") or os.path.join(HERE, "libkimi_hip.so")
-
-# every symbol include/kimi_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "kh_version", "kh_last_error", "kh_device_count", "kh_edt", "kh_edt_nd", "kh_edt_timed", "kh_label_stats", "kh_scatter_lists",
-    "kh_neighbor_mask", "kh_apply_voxel_graph", "kh_edf_batch", "kh_pdrf", "kh_trace_paths", "kh_fill_f32", "kh_fill_u8",
-    "kh_gather_f32", "kh_init_alive", "kh_level_keys", "kh_invalidate_cube", "kh_invalidate_ball", "kh_path_search", "kh_parental_field", "kh_path_from_parents", "kh_zero2inf", "kh_inf2zero", "kh_pdrf_field", "kh_target_max", "kh_find_target", "kh_first_label", "kh_ccl26", "kh_ccl26_graph", "kh_edt_graph_cells", "kh_edt_graph_sample", "kh_fill_voids", "kh_fill_voids_nd", "kh_host_ccl26", "kh_host_find_border_targets", "kh_host_merge_components",
-    "kh_host_consolidate_paths",
-    "kh_geodesic_seed", "kh_geodesic_relax", "kh_feature_relax", "kh_first_appearance", "kh_remap_u32",
-    "kh_geodesic_seed_at", "kh_box_shell_diff", "kh_first_appearance_box",
-    "kh_nearest_label_voxels", "kh_nearest_label_voxels_box", "kh_binary_edge_count", "kh_binary_edge_emit",
-    "kh_cross_sections", "kh_cross_sections_scratch_bytes", "kh_host_section_voxel", "kh_cross_sections_filled",
-    "kh_cross_sections_box", "kh_cross_sections_fixed_exponent", "kh_cross_sections_filled_box",
-    "kh_regions6", "kh_region_table", "kh_region_pairs", "kh_region_apply", "kh_host_resolve_holes", "kh_host_enclosed_regions",
-    "kh_region_table_box", "kh_region_seam_pairs", "kh_region_apply_box",
-    "kh_part_gaps", "kh_part_clusters", "kh_host_join_plan",
-    "kh_heap_script", "kh_heap_flood",
-    "kh_voxel_graph",
-    "kh_forest_components", "kh_forest_measure", "kh_forest_ticks",
-]
+HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "kimi_hip.h")
 
 
 class HipUnavailableError(RuntimeError):
@@ -42,35 +31,87 @@ class KimiHipError(RuntimeError):
     pass
 
 
-# kh_label_t  (include/kimi_hip.h) -- 55 x 4 bytes
-LABEL_T = np.dtype([
-    ("segid", "<u4"), ("list_offset", "<u4"), ("count", "<u4"), ("xmin", "<u4"), ("xmax", "<u4"),
-    ("source", "<u4"), ("max_loc", "<u4"), ("max_val", "<f4"), ("M", "<f4"), ("root", "<u4"),
-    ("q_offset", "<u4"), ("q_capacity", "<u4"), ("heap_offset", "<u4"), ("heap_capacity", "<u4"),
-    ("path_offset", "<u4"), ("path_capacity", "<u4"), ("tgt_offset", "<u4"), ("n_before", "<u4"),
-    ("n_after", "<u4"), ("max_paths", "<u4"), ("n_paths", "<u4"), ("n_vertices", "<u4"),
-    ("status", "<u4"), ("stat_settled", "<u4"), ("stat_heap_pushes", "<u4"),
-    ("cyc_target", "<u4"), ("cyc_rail", "<u4"), ("cyc_inval", "<u4"),
-    ("cyc_pop", "<u4"), ("cyc_push", "<u4"), ("cyc_fire", "<u4"),
-    ("soma_mode", "<u4"), ("fsr", "<f4"), ("soma_radius", "<f4"), ("soma_scale", "<f4"), ("soma_const", "<f4"),
-    ("nlev", "<u4"), ("sweep_rmax", "<f4"), ("ev_offset", "<u4"), ("ev_chunks", "<u4"), ("ev_shift", "<u4"),
-    ("stat_sweep_calls", "<u4"), ("stat_sweep_bails", "<u4"), ("stat_sweep_levels", "<u4"), ("stat_sweep_events", "<u4"),
-    ("stat_sweep_why", "<u4"), ("lev_window", "<u4"), ("ev_spill", "<u4"), ("stat_ghost_calls", "<u4"), ("stat_rollbacks", "<u4"),
-    ("pdrf_log2e", "<u4"), ("pdrf_scale", "<f4"),
-    ("stat_search_retries", "<u4"), ("stat_search_spills", "<u4"), ("stat_search_splits", "<u4"),
-])
+# ---- the header readers: pure functions of the header's text
+VALUE_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+               "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+RETURN_TYPES = {"int": C.c_int, "int64_t": C.c_int64}
+MEMBER_TYPES = {"uint32_t": "<u4", "float": "<f4"}
+
+
+def strip_comments(text):
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+def _param_type(func, param):
+    m = re.fullmatch(r"(.*?)\w+", param.strip(), re.S)     # everything in front of the parameter's name
+    ctype = re.sub(r"\bconst\b|\s", "", m.group(1)) if m else ""
+    if ctype.endswith("*"):
+        return C.c_char_p if ctype == "char*" else C.c_void_p
+    if ctype not in VALUE_TYPES:
+        raise TypeError("kimi_hip.h: %s has a parameter '%s' of a type the binding does not know" % (func, param.strip()))
+    return VALUE_TYPES[ctype]
+
+
+def header_prototypes(text):
+    """[(name, restype, [argtypes])] of every `type kh_name(args);`, in header order"""
+    out = []
+    for ret, name, args in re.findall(r"^([\w \t*]+?)\b(kh_\w+)\s*\(([^)]*)\)\s*;", strip_comments(text), re.M):
+        if ret.strip() not in RETURN_TYPES:
+            raise TypeError("kimi_hip.h: %s returns '%s', a type the binding does not know" % (name, ret.strip()))
+        params = [] if args.strip() == "void" else args.split(",")
+        out.append((name, RETURN_TYPES[ret.strip()], [_param_type(name, p) for p in params]))
+    return out
+
+
+def header_defines(text):
+    """{name: int} of every `#define KH_NAME value`; value is 16, 1u, 0x100 or (-1)"""
+    out = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(KH_\w+)\b(.*)$", strip_comments(text), re.M):
+        m = re.fullmatch(r"(\d+|0[xX][0-9a-fA-F]+)[uU]?|\((-\d+)\)", value.strip())
+        if not m:
+            raise ValueError("kimi_hip.h: #define %s has a value the binding cannot read: '%s'" % (name, value.strip()))
+        out[name] = int(m.group(1) or m.group(2), 0)
+    return out
+
+
+def header_struct(text, name):
+    """[(member, numpy format)] of `typedef struct name { ... } name;`, comma lists expanded"""
+    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), strip_comments(text), re.S)
+    if not m:
+        raise ValueError("kimi_hip.h: no typedef struct %s" % name)
+    out = []
+    for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+        ctype, _, members = decl.partition(" ")
+        members = [n.strip() for n in members.split(",")]
+        if ctype not in MEMBER_TYPES or not all(re.fullmatch(r"[A-Za-z_]\w*", n) for n in members):
+            raise TypeError("kimi_hip.h: %s has a member '%s' of a kind the binding does not know" % (name, decl))
+        out += [(n, MEMBER_TYPES[ctype]) for n in members]
+    return out
+
+
+# ---- the ABI, read once per process
+try:
+    with open(HEADER_PATH) as _f:
+        _header = _f.read()
+except OSError as e:
+    raise HipUnavailableError("kimimaro_amd: cannot read the C ABI %s (%s); the binding is derived from it." % (HEADER_PATH, e)) from e
+PROTOTYPES = header_prototypes(_header)
+SYMBOLS = [name for name, _, _ in PROTOTYPES]   # every symbol include/kimi_hip.h declares
+_KH = header_defines(_header)
+LABEL_T = np.dtype(header_struct(_header, "kh_label_t"))   # 55 x 4 bytes
 assert LABEL_T.itemsize == 220
-SWEEP_LDS_LEVELS = 16384  # KH_SWEEP_LDS_LEVELS
+del _header
+
+ENODEVICE = _KH["KH_ENODEVICE"]
+# KH_TRACE_* (the flags of kh_trace_paths), KH_PDRF_BASE / _FINISH / _KEEP_OTHERS and KH_HOLES_PROCESSED / _FILLED / _KILLED (the
+# label states of kh_host_resolve_holes) under their names without the KH_: TRACE_PROFILE, PDRF_BASE, HOLES_FILLED, ...
+globals().update({k[3:]: v for k, v in _KH.items() if k.startswith(("KH_TRACE_", "KH_PDRF_", "KH_HOLES_"))})
+SWEEP_LDS_LEVELS = _KH["KH_SWEEP_LDS_LEVELS"]
+BRICK = (_KH["KH_BRICK_X"], _KH["KH_BRICK_Y"], _KH["KH_BRICK_Z"])   # the activity bricks of kh_geodesic_relax / kh_feature_relax
+GRAPH_LDS_PAIRS = _KH["KH_GRAPH_LDS_PAIRS"]   # kh_voxel_graph searches a longer pair table in global memory
+# the two below have no #define in the header (it is device-visible; the library's sources hold their own): literals
 SWEEP_MAX_LEVELS = 1 << 22  # labels with more levels than this use the heap emulation only
-PDRF_BASE, PDRF_FINISH = -1, -2  # KH_PDRF_BASE / KH_PDRF_FINISH
-PDRF_KEEP_OTHERS = 0x100         # KH_PDRF_KEEP_OTHERS
-# flags of kh_trace_paths (KH_TRACE_*; tests/test_abi.py compares them with the header)
-TRACE_PROFILE, TRACE_HEAP_PRIO, TRACE_THREADS_64, TRACE_THREADS_128, TRACE_NO_GHOSTS, TRACE_GHOST_PARANOID = 1, 2, 4, 8, 16, 32
-TRACE_BIG_LDS_HEAP, TRACE_VOXEL_GRAPH, TRACE_SCRATCH_POOL, TRACE_FUSED_EDF = 64, 128, 256, 512
-HOLES_PROCESSED, HOLES_FILLED, HOLES_KILLED = 1, 2, 4    # KH_HOLES_*: the label states of kh_host_resolve_holes
-BRICK = (64, 4, 4)               # KH_BRICK_X / _Y / _Z: the activity bricks of kh_geodesic_relax / kh_feature_relax
-NO_FEATURE = 0xFFFFFFFF          # the "no seed reaches this voxel" word of kh_geodesic_seed
-GRAPH_LDS_PAIRS = 2048           # KH_GRAPH_LDS_PAIRS: kh_voxel_graph searches a longer pair table in global memory
+NO_FEATURE = 0xFFFFFFFF     # the "no seed reaches this voxel" word of kh_geodesic_seed
 
 
 def np_ptr(a):
@@ -95,9 +136,9 @@ def is_pow2_exponent(e):
                         "kimimaro/trace.py:313)")
     return i > 0 and (i & (i - 1)) == 0 and i < 2 ** 16
 
-ST_BITS = {1: "work-list overflow", 2: "invalidation heap overflow", 4: "path buffer overflow",
-           8: "no rail reachable from a target", 16: "float-absorption plateau while back-tracking",
-           32: "target outside the label"}
+ST_BITS = {_KH["KH_ST_QUEUE_OVERFLOW"]: "work-list overflow", _KH["KH_ST_HEAP_OVERFLOW"]: "invalidation heap overflow",
+           _KH["KH_ST_PATH_OVERFLOW"]: "path buffer overflow", _KH["KH_ST_NO_RAIL"]: "no rail reachable from a target",
+           _KH["KH_ST_PLATEAU"]: "float-absorption plateau while back-tracking", _KH["KH_ST_BAD_TARGET"]: "target outside the label"}
 
 _lib = None
 
@@ -120,103 +161,9 @@ def lib():
         L = C.CDLL(LIB_PATH)
     except OSError as e:  # e.g. libamdhip64 missing
         raise HipUnavailableError("kimimaro_amd: cannot load %s: %s" % (LIB_PATH, e)) from e
-    i64, f32, vp, ci = C.c_int64, C.c_float, C.c_void_p, C.c_int
-    L.kh_version.restype = ci
-    L.kh_last_error.argtypes = [C.c_char_p, ci]
-    L.kh_device_count.restype = ci
-    L.kh_edt.argtypes = [vp, ci, i64, i64, i64, f32, f32, f32, ci, vp, vp, vp]
-    L.kh_edt_nd.argtypes = [vp, ci, ci, i64, i64, i64, f32, f32, f32, ci, vp, vp, vp]
-    L.kh_edt_timed.argtypes = [vp, ci, i64, i64, i64, f32, f32, f32, ci, vp, vp, vp, vp]
-    L.kh_label_stats.argtypes = [vp, ci, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.kh_scatter_lists.argtypes = [vp, ci, i64, vp, i64, vp, vp, vp, vp]
-    L.kh_neighbor_mask.argtypes = [vp, ci, i64, i64, i64, vp, vp]
-    L.kh_edf_batch.argtypes = [vp, ci, ci, vp, vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp]
-    L.kh_pdrf.argtypes = [vp, ci, i64, vp, vp, vp, vp, ci, f32, vp, vp]
-    L.kh_trace_paths.argtypes = [vp, ci, vp, vp, vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, vp,
-                                 f32, f32, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, ci, ci, vp]
-    L.kh_invalidate_ball.argtypes = [vp, vp, vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, i64, f32, f32,
-                                     vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp]
-    L.kh_apply_voxel_graph.argtypes = [vp, vp, i64, vp, vp]
-    L.kh_path_search.argtypes = [vp, ci, vp, vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, C.c_uint64, C.c_uint64, vp, i64, vp, ci, vp]
-    L.kh_parental_field.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, C.c_uint64, vp, ci, vp]
-    L.kh_path_from_parents.argtypes = [vp, i64, C.c_uint64, vp, i64, vp, vp]
-    L.kh_zero2inf.argtypes = [vp, i64, vp]
-    L.kh_inf2zero.argtypes = [vp, i64, vp]
-    L.kh_pdrf_field.argtypes = [vp, vp, i64, f32, ci, f32, f32, vp, vp]
-    L.kh_target_max.argtypes = [vp, vp, vp, i64, vp, vp]
-    L.kh_find_target.argtypes = [vp, vp, i64, i64, i64, vp, vp]
-    L.kh_first_label.argtypes = [vp, i64, vp, vp]
-    L.kh_level_keys.argtypes = [i64, i64, i64, f32, f32, f32, vp, vp]
-    L.kh_fill_f32.argtypes = [vp, i64, f32, vp]
-    L.kh_fill_u8.argtypes = [vp, i64, ci, vp]
-    L.kh_gather_f32.argtypes = [vp, vp, i64, vp, vp]
-    L.kh_init_alive.argtypes = [vp, ci, i64, vp, vp, vp]
-    L.kh_invalidate_cube.argtypes = [vp, vp, i64, i64, i64, f32, f32, f32, vp, i64, f32, f32, vp, vp]
-    L.kh_ccl26.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.kh_ccl26_graph.argtypes = [vp, ci, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]
-    L.kh_edt_graph_cells.argtypes = [vp, ci, vp, i64, i64, i64, ci, vp, vp]
-    L.kh_edt_graph_sample.argtypes = [vp, i64, i64, i64, vp, vp]
-    L.kh_fill_voids.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp]
-    L.kh_fill_voids_nd.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp]
-    L.kh_host_ccl26.argtypes = [vp, ci, i64, i64, i64, vp]
-    L.kh_host_ccl26.restype = i64
-    L.kh_host_find_border_targets.argtypes = [vp, vp, i64, i64, f32, f32, i64, vp, vp]
-    L.kh_host_find_border_targets.restype = i64
-    L.kh_host_merge_components.argtypes = [i64, vp, vp, vp, vp, vp, vp, i64, i64, f32, f32, f32, vp, vp, vp]
-    L.kh_host_merge_components.restype = i64
-    L.kh_host_consolidate_paths.argtypes = [i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp]
-    L.kh_host_consolidate_paths.restype = i64
-    L.kh_geodesic_seed.argtypes = [vp, vp, i64, vp, ci, vp, i64, vp, vp, vp]
-    L.kh_geodesic_relax.argtypes = [vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, ci, i64, vp]
-    L.kh_feature_relax.argtypes = [vp, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, ci, i64, vp]
-    L.kh_first_appearance.argtypes = [vp, i64, i64, vp, vp]
-    L.kh_remap_u32.argtypes = [vp, vp, i64, i64, vp]
-    L.kh_geodesic_seed_at.argtypes = [vp, vp, i64, vp, ci, vp, i64, vp, vp, vp]
-    L.kh_box_shell_diff.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp]
-    L.kh_first_appearance_box.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, i64, i64, vp, vp]
-    L.kh_nearest_label_voxels.argtypes = [vp, ci, i64, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp]
-    L.kh_nearest_label_voxels_box.argtypes = [vp, ci, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp]
-    L.kh_binary_edge_count.argtypes = [vp, i64, C.c_uint32, vp, vp, vp, vp]
-    L.kh_binary_edge_emit.argtypes = [vp, i64, i64, i64, C.c_uint32, vp, vp, vp, vp, vp]
-    f64 = C.c_double
-    L.kh_cross_sections.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.kh_cross_sections_scratch_bytes.argtypes = [i64, i64, i64, i64]
-    L.kh_cross_sections_scratch_bytes.restype = i64
-    L.kh_host_section_voxel.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp]
-    L.kh_cross_sections_filled.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.kh_cross_sections_box.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, i64, i64, i64, i64, i64, i64, ci, vp, vp, vp, vp,
-                                        vp, i64, vp]
-    L.kh_cross_sections_fixed_exponent.argtypes = [i64, i64, i64, f64, f64, f64]
-    L.kh_cross_sections_filled_box.argtypes = [vp, ci, i64, i64, i64, f64, f64, f64, i64, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64,
-                                               i64, ci, vp, vp, vp, vp, vp, i64, vp]
-    L.kh_regions6.argtypes = [vp, ci, i64, i64, i64, vp, vp, vp, vp, vp, vp]
-    L.kh_region_table.argtypes = [vp, ci, vp, vp, i64, ci, i64, i64, i64, vp, vp, vp, vp]
-    L.kh_region_pairs.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp]
-    L.kh_region_apply.argtypes = [vp, vp, vp, ci, i64, vp]
-    L.kh_region_table_box.argtypes = [vp, ci, vp, vp, i64, ci, i64, i64, i64, C.c_uint32, vp, vp, vp, vp]
-    L.kh_region_seam_pairs.argtypes = [vp, vp, i64, vp, i64, vp, vp]
-    L.kh_region_apply_box.argtypes = [vp, C.c_uint32, i64, vp, vp, ci, i64, vp, vp]
-    L.kh_host_resolve_holes.argtypes = [i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]
-    L.kh_host_resolve_holes.restype = i64
-    L.kh_host_enclosed_regions.argtypes = [i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]
-    L.kh_host_enclosed_regions.restype = i64
-    L.kh_part_gaps.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]
-    L.kh_part_clusters.argtypes = [vp, vp, vp, vp, i64, i64, ci, vp, vp]
-    L.kh_host_join_plan.argtypes = [i64, vp, vp, vp, vp, f64, ci, vp]
-    L.kh_host_join_plan.restype = i64
-    L.kh_heap_script.argtypes = [ci, vp, i64, vp, i64, C.c_uint32, vp, i64, vp, i64, vp, vp]
-    L.kh_heap_flood.argtypes = [ci, ci, i64, i64, i64, f32, f32, f32, vp, vp, vp, vp, vp, i64, f32, f32, C.c_uint32, C.c_uint32,
-                                vp, i64, C.c_uint32, vp, vp, vp]
-    L.kh_voxel_graph.argtypes = [vp, ci, i64, i64, i64, ci, vp, i64, vp, vp]
-    L.kh_forest_components.argtypes = [vp, i64, i64, vp, vp]
-    L.kh_forest_measure.argtypes = [vp, vp, vp, i64, i64, vp, vp, vp, vp, vp]
-    L.kh_forest_ticks.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i64, f64, vp, vp, vp, vp, vp, vp, vp]
-    for name in SYMBOLS:
-        getattr(L, name)
-        if name not in ("kh_version", "kh_device_count", "kh_host_ccl26", "kh_last_error", "kh_cross_sections_scratch_bytes",
-                        "kh_host_find_border_targets", "kh_host_merge_components", "kh_host_consolidate_paths",
-                        "kh_host_resolve_holes", "kh_host_enclosed_regions", "kh_host_join_plan"):
-            getattr(L, name).restype = ci
+    for name, restype, argtypes in PROTOTYPES:
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -231,7 +178,7 @@ def check(rc):
     if rc == 0:
         return
     msg = last_error()
-    if rc == 3:
+    if rc == ENODEVICE:
         raise HipUnavailableError(msg)
     raise KimiHipError("libkimi_hip error %d: %s" % (rc, msg))
 
