@@ -40,6 +40,7 @@ namespace kh {
 constexpr int XS_LDS_QUEUE = 2048;        // queue entries per wave in LDS: 8 KiB per wave, 32 KiB per block of four waves
 constexpr int XS_WAVES_PER_BLOCK = 4;
 constexpr int64_t XS_HEADER_BYTES = 256;  // scratch: [0] the item counter, [1] the overflow flag
+// What a launch leaves in the scratch, and that every wave count gives the same bytes: DESIGN.md 3.12 "The scratch after a launch".
 
 // d of DESIGN.md 3.12: ((nx ax) dx + (ny ay) dy) + (nz az) dz, left to right; h likewise
 __host__ __device__ inline double xs_offset(double nax, double nay, double naz, int dx, int dy, int dz) {
@@ -396,6 +397,10 @@ static int xs_launch(const char* name, const void* labels, int label_bytes, int6
     set_error("%s: region, hole_begin, hole_count and hole_regions must not be null", name);
     return KH_EINVAL;
   }
+  if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4) {       // before the memset below: a refused call writes nothing
+    set_error("%s: label_bytes must be 1, 2 or 4", name);
+    return KH_EINVAL;
+  }
   int64_t waves = (scratch_bytes - XS_HEADER_BYTES) / L.wave_bytes;
   if (scratch_bytes < XS_HEADER_BYTES || waves < 1 || ((uintptr_t)scratch & 7)) {
     set_error("%s: the scratch holds no wave (kh_cross_sections_scratch_bytes) or is not 8-byte aligned", name);
@@ -451,7 +456,7 @@ static int xs_launch(const char* name, const void* labels, int label_bytes, int6
     case 1: KH_XS_LAUNCH(uint8_t); break;
     case 2: KH_XS_LAUNCH(uint16_t); break;
     case 4: KH_XS_LAUNCH(uint32_t); break;
-    default: set_error("%s: label_bytes must be 1, 2 or 4", name); return KH_EINVAL;
+    default: break;       // (refused above)
   }
 #undef KH_XS_LAUNCH
   KH_LAUNCH_CHECK();
