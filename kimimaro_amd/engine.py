@@ -70,7 +70,7 @@ class Engine:
         self.path_gate = None
         self.heap_prio = os.environ.get("KH_HEAP_PRIO", "0") == "1"         # s_setprio 3 for the heap-emulation wave (A/B knob)
         self.sweep_window = os.environ.get("KH_SWEEP_WINDOW", "1") != "0"   # level words for a window of levels only (A/B knob)
-        # ghosts (DESIGN.md 3.4.6): a call of the sweep that leaves voxels undecided goes on with them as ghosts instead of running
+        # ghosts (DESIGN.md 3.4.5): a call of the sweep that leaves voxels undecided goes on with them as ghosts instead of running
         # the heap emulation at once; "paranoid" rolls every such call back at once (a test of the roll-back; results identical)
         self.ghosts = os.environ.get("KH_GHOSTS", "1") != "0"
         self.ghost_paranoid = os.environ.get("KH_GHOSTS", "1") == "paranoid"

@@ -68,9 +68,15 @@ def _nhood26(x, y, z, sx, sy, sz, quirk=True):
     return nb
 
 
-def sweep_model(mask, anisotropy, path, radii, graph=None, trace=False, x_face_quirk=True):
+def sweep_model(mask, anisotropy, path, radii, graph=None, trace=False, x_face_quirk=True, ghosts=None):
     """The machine on one call.  mask: uint8 (x, y, z), non-zero = alive (not changed); path: (n, 3) voxels; radii: float32 per path
     vertex; graph: optional uint32 voxel connectivity graph of the mask's shape; x_face_quirk=False: see _nhood26.
+    ghosts: the linear indices of the alive voxels that an earlier call left undecided (csrc/sweep.h:1025-1031, :670-673): a ghost
+    takes candidates and hands P events on like any alive voxel; a D event on it makes it D and is counted apart (KG); it sends no
+    D events itself -- its candidates' P events went out when they joined.  A path vertex that is a ghost is a source like an alive
+    one (sweep.h:1078 tests the alive byte for non-zero): its own D event at level 0 kills it for certain and stops there, its P
+    event goes on.  With ghosts the result carries D (every voxel that became D, ghosts among them), KG (the ghosts among D), M
+    (every voxel left with candidates, old ghosts among them) and made (M without the old ghosts: the ghosts this call makes).
     Returns a namespace: D, M (sorted arrays of Fortran-order linear indices), certified, count (= |D|), max_cand (largest
     |Cand(v)| any voxel ever held), max_cand_at_death (largest |Cand(v)| of a voxel at its D event), n_many (voxels that ever held
     five candidates or more), levels (non-empty levels), peak_levels (most levels that had events pending at one time) and, with
@@ -86,6 +92,9 @@ def sweep_model(mask, anisotropy, path, radii, graph=None, trace=False, x_face_q
     rad = [float(np.float32(r)) for r in np.asarray(radii, dtype=np.float32).reshape(-1)]
     assert len(rad) == len(pts)
     src = [(int(p[0]), int(p[1]), int(p[2])) for p in pts]
+    ghost = frozenset(int(v) for v in np.asarray(ghosts if ghosts is not None else [], dtype=np.int64).reshape(-1))
+    assert all(alive0[v] for v in ghost), "a ghost is an alive voxel of the mask"
+    KG = []
 
     nbr_cache = {}
 
@@ -184,6 +193,9 @@ def sweep_model(mask, anisotropy, path, radii, graph=None, trace=False, x_face_q
             D.append(v)
             if len(cs) > max_death:
                 max_death = len(cs)
+            if v in ghost:                         # it may have been dead all along: no D events from it
+                KG.append(v)
+                continue
             owners = [(src[c], rad[c]) for c in cs]
             for q, qx, qy, qz in nbrs(v):
                 if dead[q]:
@@ -208,7 +220,8 @@ def sweep_model(mask, anisotropy, path, radii, graph=None, trace=False, x_face_q
     M = sorted(v for v, cs in cand.items() if cs)
     return SimpleNamespace(D=np.array(sorted(D), dtype=np.int64), M=np.array(M, dtype=np.int64), certified=not M, count=len(D),
                            max_cand=max_cand, max_cand_at_death=max_death, n_many=n_many, levels=levels, peak_levels=peak,
-                           ahead=ahead)
+                           ahead=ahead, KG=np.array(sorted(KG), dtype=np.int64),
+                           made=np.array([v for v in M if v not in ghost], dtype=np.int64))
 
 
 def classify(res):

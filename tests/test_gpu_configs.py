@@ -114,7 +114,7 @@ def test_c2_full_size_every_skeleton(eng, c2):
 
 @pytest.mark.parametrize("mode", ["ghosts", "paranoid", "off"])
 def test_c2_ghost_modes_every_skeleton(c2, mode):
-    """DESIGN.md 3.4.6 at full size: c2 traced with ghosts (the default: a call of the sweep that leaves voxels undecided goes on
+    """DESIGN.md 3.4.5 at full size: c2 traced with ghosts (the default: a call of the sweep that leaves voxels undecided goes on
     with them as ghosts, the label rolls back only when a ghost would matter), with every ghost call rolled back at once (the
     roll-back path itself: journal revival, rail weights restored, the call redone by the heap emulation) and with ghosts off
     (rounds 2-4) -- all three equal to the pooled oracle, skeleton by skeleton.  The counters prove the paths ran."""
