@@ -827,6 +827,47 @@ int kh_forest_ticks(const float* xyz, const uint32_t* row_start, const uint32_t*
                     int64_t nverts, int64_t nslots, int64_t ncrit, int64_t ncomps, double threshold, uint32_t* slot_scratch,
                     int32_t* arity, uint32_t* rec_scratch, double* rec_len, uint8_t* rec_flag, uint8_t* alive, void* stream);
 
+/* ---- the path walk on the forest form (csrc/walk.hip) ------------------------------------------------------------
+ * replaces: Skeleton.paths() and the per-path numpy of utility._xs_occurrences, for every tree of a call at once.  Both calls are
+ * asynchronous on `stream`, allocate nothing, use no atomics and are built with -ffp-contract=off.
+ *
+ * kh_walk_orient: adjacency as for kh_forest_ticks (row_start u32 [nverts+1], nbr u32 [nslots], the distinct neighbours of a vertex
+ * ascending, no self loops); comp u32 [nverts] as kh_forest_components writes it.  A listed component is a TREE of two vertices or
+ * more (the caller checks ne == nv - 1), given by its critical vertices, ascending: those of degree 1 or >= 3 AND its smallest
+ * vertex (comp[v] == v) whatever its degree: crit u32 [ncrit], component c at [crit_start[c], crit_start[c+1]), crit_start u32
+ * [ncomps+1].  leaf_start u32 [ncomps+1]: the prefix sum of (vertices of degree 1) - 1 per listed component; npaths = its last word.
+ * Output, every word written:
+ *   parent, depth u32 [nverts]   the tree oriented from its root: the vertex farthest in hops from the component's smallest vertex,
+ *                                the smallest index among equally far ones.  The root, and every vertex of no listed component,
+ *                                has parent 0xFFFFFFFF and depth 0.
+ *   path_leaf, path_len u32 [npaths]   at leaf_start[c] + k the k-th leaf of component c in the order a depth-first walk from the
+ *                                root reaches them when it takes neighbours in ascending index (the vertices of degree 1 but the
+ *                                root, in preorder), and depth + 1, the vertices of the path root .. leaf.
+ * Scratch, sized by the caller: slot_scratch u32 [3*nslots] (far, twin, hops per slot of a critical vertex), rec_scratch u32
+ * [8*ncrit] (per record of the oriented contracted tree: vertex, slot to the parent, depth, first child, children, first record of
+ * round b, leaves below, leaves before).  A thread per critical vertex walks its chains; ONE WAVE per component orients the
+ * contracted tree, twice (from the smallest vertex for the hops, from the root), counts the leaves bottom-up and places them
+ * top-down; a thread per record writes parent / depth along its chain.  0 <= nverts, nslots < 2^31.                              */
+int kh_walk_orient(const uint32_t* row_start, const uint32_t* nbr, const uint32_t* comp, const uint32_t* crit,
+                   const uint32_t* crit_start, const uint32_t* leaf_start, int64_t nverts, int64_t nslots, int64_t ncrit,
+                   int64_t ncomps, int64_t npaths, uint32_t* slot_scratch, uint32_t* rec_scratch, uint32_t* parent, uint32_t* depth,
+                   uint32_t* path_leaf, uint32_t* path_len, void* stream);
+
+/* kh_walk_emit: parent, path_leaf as above; pstart i64 [npaths+1], the prefix sum of path_len (pstart[0] = 0, pstart[npaths] =
+ * nocc < 2^31); vox i32 [nverts,3], every vertex's voxel.
+ * Output: occ_vertex u32 [nocc], every word written: at [pstart[p], pstart[p+1]) the vertices of path p from the root to the leaf;
+ * normal f64 [nocc,3] (window >= 1; with window 0 it is not touched and may be null): the unit normals of
+ * kimimaro.utility's section loop along every path.  d_j = vox[next] - vox[this], the last vertex repeats the last difference.
+ *   window 1: float32 d / sqrtf(((dx*dx) + (dy*dy)) + (dz*dz)), root and quotient correctly rounded, then widened; a thread per
+ *             occurrence.
+ *   window n > 1: f64 throughout, |d| < 2^24; two moving averages over the input extended by n entries on both sides by reflection
+ *             (np.pad "symmetric": j mod 2L, mirrored above L): forwards (sums of integers, exact), then over the reversed result,
+ *             where R is the SEQUENTIAL running sum in padded order and out = (R[i + n] - R[i]) / n -- numpy's cumsum, addition by
+ *             addition -- then v / sqrt(((x*x) + (y*y)) + (z*z)).  A thread per path; first f64 [nocc,3] is its scratch.
+ * A zero vector gives NaN in all three components.                                                                              */
+int kh_walk_emit(const uint32_t* parent, const uint32_t* path_leaf, const int64_t* pstart, const int32_t* vox, int64_t nverts,
+                 int64_t npaths, int64_t nocc, int window, uint32_t* occ_vertex, double* normal, double* first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

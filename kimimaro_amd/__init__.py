@@ -14,7 +14,7 @@ from .intake import DEFAULT_TEASAR_PARAMS, DimensionError, connect_points, skele
 from .lanes import skeletonize_many  # noqa: F401
 from .ops import voxel_connectivity_graph  # noqa: F401
 from .post import (components_many, cross_sectional_area_chunked, cross_sectional_area_filled_chunked, fill_all_holes_chunked,  # noqa: F401
-                   join_close_components, join_close_components_many, oversegment_chunked, postprocess, postprocess_many,
+                   join_close_components, join_close_components_many, oversegment_chunked, paths_many, postprocess, postprocess_many,
                    remove_dust_many, remove_loops_many, remove_ticks_many, skeletonize_chunked, skeletonize_graph_chunked,
                    synapses_to_targets_chunked, voxel_connectivity_graph_chunked)
 from .skeleton import Skeleton  # noqa: F401

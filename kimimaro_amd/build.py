@@ -13,7 +13,7 @@ from ._abi import HEADER_PATH
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libkimi_hip.so")
-SOURCES = ["common.hip", "edt.hip", "prep.hip", "trace.hip", "heap_script.hip", "heap_flood.hip", "ccl.hip", "feature.hip", "points.hip", "section.hip", "join.hip", "graph.hip", "forest.hip"]
+SOURCES = ["common.hip", "edt.hip", "prep.hip", "trace.hip", "heap_script.hip", "heap_flood.hip", "ccl.hip", "feature.hip", "points.hip", "section.hip", "join.hip", "graph.hip", "forest.hip", "walk.hip"]
 # what a change of asks for a rebuild (paths from CSRC; the last is absolute): the sources, EVERY header next to them, the C ABI
 DEPS = SOURCES + sorted(os.path.basename(h) for h in glob.glob(os.path.join(CSRC, "*.h"))) + [HEADER_PATH]
 

@@ -11,9 +11,14 @@ and remove_ticks_many are written on it.
     unpack_components / _dust / _ticks   device results -> Skeletons, vectorised over the whole batch (stable argsort by label,
                                      rank renumbering, np.split); the only Python loops run over skeletons and components, to
                                      construct the objects
+    Walk, WalkTables, walk(...)      the path walk (csrc/walk.hip): skeletons AS GIVEN back to back, what kh_walk_orient
+                                     is given, and walk_labels / walk_orient / walk_emit around the device calls -> Walked, the paths
+                                     of every tree of the call; post.paths_many and utility._xs_occurrences_many are written on it
 
 The library allocates nothing: every output and scratch buffer is sized here."""
 from __future__ import annotations
+
+import time
 
 import numpy as np
 
@@ -217,6 +222,222 @@ def ticks(eng, forest, measures, threshold):
     _abi.check(eng.lib.kh_forest_ticks(P(d_xyz), P(d_row), P(d_nbr), P(d_crit), P(d_cstart), n, nslots, ncrit, ncomps, float(threshold),
                                        P(d_slots), P(d_arity), P(d_recs), P(d_len), P(d_flag), P(d_alive), eng.stream()))
     return d_alive.cpu().numpy()[upper] != 0
+
+
+# ---- the path walk (csrc/walk.hip) --------------------------------------------------------------------------------
+VOX_LIMIT = 2 ** 23               # |voxel coordinate| below this: a difference of two is an exact float32, as kh_walk_emit takes it
+
+
+class Walk:
+    """Skeletons AS GIVEN, back to back: vstart i64 [S + 1] counts every vertex of every skeleton (the numbers are the caller's; a
+    vertex without an edge stays where it is), edges u32 [M, 2] the distinct (lo, hi) rows without self loops in call-wide numbering,
+    ascending -- what Skeleton._neighbours makes of repeated, reversed, shuffled rows and self loops -- and their CSR adjacency
+    row_start u32 [V + 1], nbr u32 [2M].  dev: what the device calls keep for each other between walk_labels, walk_orient and
+    walk_emit."""
+
+    def __init__(self, skeletons, limit=None):
+        limit = LIMIT if limit is None else int(limit)
+        self.skeletons = list(skeletons)
+        nv = np.array([np.asarray(s.vertices).reshape(-1, 3).shape[0] for s in self.skeletons], dtype=np.int64)
+        ne = np.array([np.asarray(s.edges).reshape(-1, 2).shape[0] for s in self.skeletons], dtype=np.int64)
+        self.vstart = np.concatenate([[0], np.cumsum(nv)]).astype(np.int64)
+        if int(self.vstart[-1]) >= limit or 2 * int(ne.sum()) >= limit:
+            raise ValueError("the walk holds %d vertices and %d edge rows: one device call takes fewer than %d vertices and %d rows"
+                             % (self.vstart[-1], ne.sum(), limit, limit // 2))
+        rows = [np.asarray(s.edges, dtype=np.int64).reshape(-1, 2) for s in self.skeletons if np.asarray(s.edges).size]
+        local = np.concatenate(rows) if rows else np.zeros((0, 2), dtype=np.int64)
+        owner = np.repeat(np.arange(len(self.skeletons)), ne)
+        if local.size and (local.min() < 0 or np.any(local.max(axis=1) >= nv[owner])):
+            k = int(owner[np.flatnonzero((local.max(axis=1) >= nv[owner]) | (local.min(axis=1) < 0))[0]])
+            raise ValueError("skeleton %d: an edge names a vertex outside its %d vertices" % (k, nv[k]))
+        keep = local[:, 0] != local[:, 1]
+        e = local[keep] + self.vstart[owner[keep]][:, None]
+        key = np.unique((e.min(axis=1) << 32) | e.max(axis=1))
+        self.edges = np.stack([key >> 32, key & 0xFFFFFFFF], axis=1).astype(np.uint32)
+        self.row_start, self.nbr, _ = adjacency(self.edges, self.nverts)
+        self.degree = np.diff(self.row_start.astype(np.int64))
+        self.dev = {}
+
+    @property
+    def nverts(self):
+        return int(self.vstart[-1])
+
+    def skeleton_of_vertex(self, v):
+        return np.searchsorted(self.vstart, v, side="right") - 1
+
+
+def walk_batches(skeletons, limit=None):
+    """the list cut between skeletons into slices of fewer than `limit` (default LIMIT) vertices and adjacency slots each; ValueError
+    for a single skeleton at or beyond it"""
+    limit = LIMIT if limit is None else int(limit)
+    out, first, v, e = [], 0, 0, 0
+    for k, s in enumerate(skeletons):
+        nv, ns = int(np.asarray(s.vertices).reshape(-1, 3).shape[0]), 2 * int(np.asarray(s.edges).reshape(-1, 2).shape[0])
+        if nv >= limit or ns >= limit:
+            raise ValueError("skeleton %d has %d vertices and %d edge rows: one device call takes fewer than %d vertices and %d rows"
+                             % (k, nv, ns // 2, limit, limit // 2))
+        if v + nv >= limit or e + ns >= limit:
+            out.append(slice(first, k))
+            first, v, e = k, 0, 0
+        v, e = v + nv, e + ns
+    out.append(slice(first, len(skeletons)))
+    return out
+
+
+class WalkTables:
+    """What kh_walk_orient is given beside the adjacency, from comp and the degrees (numpy): host bool [S], the skeletons with a
+    cyclic component (they are walked by the host whole and none of their components is listed); root i64 [K], the smallest vertex of
+    every listed component -- the trees of two vertices or more of the other skeletons, ascending; crit u32 [C], crit_start u32
+    [K + 1]: their critical vertices (degree 1 or >= 3, and the smallest vertex whatever its degree), ascending; leaf_start u32
+    [K + 1]: the prefix sum of their paths, (vertices of degree 1) - 1 each."""
+
+    def __init__(self, walk, comp):
+        comp = np.asarray(comp).astype(np.int64)
+        n, degree = comp.size, walk.degree
+        nv = np.bincount(comp, minlength=n)
+        slots = np.bincount(comp, weights=degree, minlength=n).astype(np.int64)       # twice the edges, exact below 2^53
+        proper = nv >= 2
+        tree = proper & (slots == 2 * (nv - 1))
+        self.host = np.zeros(len(walk.skeletons), dtype=bool)
+        self.host[walk.skeleton_of_vertex(np.flatnonzero(proper & ~tree))] = True
+        listed = tree.copy()
+        at = np.flatnonzero(tree)
+        listed[at] = ~self.host[walk.skeleton_of_vertex(at)]
+        self.root = np.flatnonzero(listed)
+        crit = np.flatnonzero(listed[comp] & ((degree != 2) | (comp == np.arange(n))))
+        crit = crit[np.argsort(comp[crit], kind="stable")]
+        index = np.cumsum(listed) - 1                                                  # at a listed root: its place in the list
+        of = index[comp[crit]]
+        self.crit = crit.astype(np.uint32)
+        self.crit_start = np.concatenate([[0], np.cumsum(np.bincount(of, minlength=self.root.size))]).astype(np.uint32)
+        leaves = np.bincount(of[degree[crit] == 1], minlength=self.root.size) - 1
+        self.leaf_start = np.concatenate([[0], np.cumsum(leaves)]).astype(np.uint32)
+
+    @property
+    def npaths(self):
+        return int(self.leaf_start[-1])
+
+
+def walk_labels(eng, walk):
+    """kh_forest_components on a Walk -> comp u32 [V] (host); the device copy and the adjacency stay in walk.dev"""
+    t, P = eng.torch, eng.ptr
+    n, m = walk.nverts, int(walk.edges.shape[0])
+    if n == 0:
+        return np.zeros(0, dtype=np.uint32)
+    d_edges = _up(eng, walk.edges) if m else None
+    d_comp = eng.empty(n, t.int32)
+    _abi.check(eng.lib.kh_forest_components(eng.optr(d_edges), n, m, P(d_comp), eng.stream()))
+    walk.dev["comp"] = d_comp
+    return d_comp.cpu().numpy().view(np.uint32)
+
+
+def walk_orient(eng, walk, tables):
+    """kh_walk_orient -> path_len u32 [npaths] (host): the vertices of every path, the components' in the order of `tables`.  parent and
+    path_leaf stay on the device, in walk.dev, for walk_emit."""
+    t, P = eng.torch, eng.ptr
+    n, ns, nc, k, npaths = walk.nverts, int(walk.nbr.size), int(tables.crit.size), int(tables.root.size), tables.npaths
+    if k == 0:
+        return np.zeros(0, dtype=np.uint32)
+    d_row, d_nbr, d_crit, d_cstart, d_lstart = (_up(eng, a) for a in (walk.row_start, walk.nbr, tables.crit, tables.crit_start,
+                                                                         tables.leaf_start))
+    d_slots, d_recs = eng.empty(3 * ns, t.int32), eng.empty(8 * nc, t.int32)
+    d_parent, d_depth = eng.empty(n, t.int32), eng.empty(n, t.int32)
+    d_leaf, d_len = eng.empty(npaths, t.int32), eng.empty(npaths, t.int32)
+    _abi.check(eng.lib.kh_walk_orient(P(d_row), P(d_nbr), P(walk.dev["comp"]), P(d_crit), P(d_cstart), P(d_lstart), n, ns, nc, k, npaths,
+                                      P(d_slots), P(d_recs), P(d_parent), P(d_depth), P(d_leaf), P(d_len), eng.stream()))
+    walk.dev["parent"], walk.dev["leaf"] = d_parent, d_leaf
+    return d_len.cpu().numpy().view(np.uint32)
+
+
+def walk_emit(eng, walk, first, last, pstart, vox, window):
+    """kh_walk_emit for the paths [first, last): pstart i64 [last - first + 1] from 0; vox i32 [V, 3] or None with window 0 ->
+    (occ_vertex u32 [m], normal f64 [m, 3] or None), host arrays"""
+    t, P = eng.torch, eng.ptr
+    m = int(pstart[-1])
+    if last == first or m == 0:
+        return np.zeros(0, dtype=np.uint32), (np.zeros((0, 3), dtype=np.float64) if window else None)
+    key = "vox"
+    if window and key not in walk.dev:
+        walk.dev[key] = eng.torch.from_numpy(np.ascontiguousarray(vox, dtype=np.int32).reshape(-1)).to(eng.device)
+    d_pstart = eng.torch.from_numpy(np.ascontiguousarray(pstart, dtype=np.int64)).to(eng.device)
+    d_occ = eng.empty(m, t.int32)
+    d_normal = eng.empty(3 * m, t.float64) if window else None
+    d_first = eng.empty(3 * m, t.float64) if window > 1 else None
+    _abi.check(eng.lib.kh_walk_emit(P(walk.dev["parent"]), P(walk.dev["leaf"][first:last]), P(d_pstart), eng.optr(walk.dev.get(key)),
+                                    walk.nverts, last - first, m, int(window), P(d_occ), eng.optr(d_normal), eng.optr(d_first),
+                                    eng.stream()))
+    occ = d_occ.cpu().numpy().view(np.uint32)
+    return occ, (d_normal.cpu().numpy().reshape(-1, 3) if window else None)
+
+
+class Walked:
+    """The paths of a call: host bool [S] (the skeletons with a cyclic component: not walked); pcut i64 [S + 1], the paths of skeleton
+    k are [pcut[k], pcut[k + 1]), in the order of Skeleton.paths(); pstart i64 [P + 1], path p is occ[pstart[p]:pstart[p + 1]], root
+    first; occ i64 [m] in call-wide numbering (vstart i64 [S + 1]); normal f64 [m, 3] or None; degree i64 [V], the distinct
+    neighbours of every vertex."""
+
+    def __init__(self, host, pcut, pstart, occ, normal, vstart, degree):
+        self.host, self.pcut, self.pstart, self.occ, self.normal, self.vstart, self.degree = host, pcut, pstart, occ, normal, vstart, degree
+
+    def paths(self, k):
+        """Skeleton.paths(return_indices=True) of skeleton k"""
+        cut = self.pstart[self.pcut[k]:self.pcut[k + 1] + 1]
+        own = self.occ[cut[0]:cut[-1]] - self.vstart[k]
+        return np.split(own, cut[1:-1] - cut[0]) if cut.size > 1 else []
+
+
+def walk(eng, skeletons, vox=None, window=0, stats=None, limit=None):
+    """The paths of every skeleton of the list in one pass (walk_batches cuts a list too long for it) -> Walked.  vox: with
+    window >= 1 the voxel of every vertex of the call, int64 [V, 3], |coordinate| < VOX_LIMIT wherever a path runs; the normals are
+    kh_walk_emit's.  ValueError for a skeleton whose occurrences alone reach `limit` (default LIMIT).  stats: walk_s (the device
+    calls with their copies), pack_s (the numpy around them) and walk_host are added to."""
+    limit = LIMIT if limit is None else int(limit)
+    t0 = time.perf_counter()
+    w = Walk(skeletons, limit)
+    nskel = len(w.skeletons)
+    t1 = time.perf_counter()
+    comp = walk_labels(eng, w)
+    t2 = time.perf_counter()
+    tables = WalkTables(w, comp)
+    t3 = time.perf_counter()
+    path_len = walk_orient(eng, w, tables).astype(np.int64)
+    device_s = (t2 - t1) + (time.perf_counter() - t3)
+    # the paths of a skeleton are consecutive: its components are, by smallest vertex
+    paths_of = np.zeros(nskel, dtype=np.int64)
+    np.add.at(paths_of, w.skeleton_of_vertex(tables.root), np.diff(tables.leaf_start.astype(np.int64)))
+    pcut = np.concatenate([[0], np.cumsum(paths_of)]).astype(np.int64)
+    pstart = np.concatenate([[0], np.cumsum(path_len)]).astype(np.int64)
+    occ_of = pstart[pcut[1:]] - pstart[pcut[:-1]]
+    if window:
+        vox = np.asarray(vox, dtype=np.int64).reshape(-1, 3)
+        assert vox.shape[0] == w.nverts
+    # the emit calls: skeletons [a, b) with fewer than `limit` occurrences together
+    occ_parts, normal_parts, a = [], [], 0
+    while a < nskel:
+        b, m = a, 0
+        while b < nskel and m + int(occ_of[b]) < limit:
+            m += int(occ_of[b])
+            b += 1
+        if b == a:
+            raise ValueError("skeleton %d has %d vertices on its paths: one device call takes fewer than %d" % (a, occ_of[a], limit))
+        first, last = int(pcut[a]), int(pcut[b])
+        t4 = time.perf_counter()
+        occ, normal = walk_emit(eng, w, first, last, pstart[first:last + 1] - pstart[first], vox, window)
+        device_s += time.perf_counter() - t4
+        occ_parts.append(occ.astype(np.int64))
+        normal_parts.append(normal)
+        a = b
+    if not occ_parts:
+        occ_parts, normal_parts = [np.zeros(0, dtype=np.int64)], [np.zeros((0, 3), dtype=np.float64)]
+    occ = np.concatenate(occ_parts) if len(occ_parts) != 1 else occ_parts[0]
+    normal = None
+    if window:
+        normal = np.concatenate(normal_parts) if len(normal_parts) != 1 else normal_parts[0]
+    if stats is not None:
+        stats["walk_s"] = stats.get("walk_s", 0.0) + device_s
+        stats["pack_s"] = stats.get("pack_s", 0.0) + (time.perf_counter() - t0) - device_s
+        stats["walk_host"] = stats.get("walk_host", 0) + int(tables.host.sum())
+    return Walked(tables.host, pcut, pstart, occ, normal, w.vstart, w.degree)
 
 
 # ---- back to Skeletons ------------------------------------------------------------------------------------------------------------

@@ -514,3 +514,12 @@ def skeleton_component_labels(skeleton):
     Skeleton.components() lists them, are the distinct values in ascending order."""
     eng = engine()
     return forest.labels(eng, forest.pack([skeleton.consolidate()]))
+
+
+def skeleton_paths(skeleton, return_indices=True):
+    """Skeleton.paths(return_indices=...) of ONE skeleton as given, walked on the device where it is a forest (kh_walk_orient,
+    kh_walk_emit): what paths_many returns for it.  A skeleton with a cyclic component is walked by the host."""
+    eng = engine()
+    w = forest.walk(eng, [skeleton])
+    paths = skeleton.paths(return_indices=True) if w.host[0] else w.paths(0)
+    return paths if return_indices else [skeleton.vertices[p] for p in paths]

@@ -305,6 +305,28 @@ def components_many(skeletons):
     return out
 
 
+def paths_many(skeletons, return_indices=True, stats=None):
+    """[s.paths(return_indices=...) for s in skeletons], array for array, every tree of the list walked in one pass on the device
+    (kh_walk_orient, kh_walk_emit).  The skeletons are taken AS GIVEN, not consolidated: vertex numbers are the
+    caller's, and self loops, repeated, reversed and unsorted rows and vertices without an edge mean what Skeleton._neighbours makes
+    of them.  Where the depth-first walk cuts a cycle is sequential: a skeleton with a cyclic component is walked by Skeleton.paths
+    whole.  stats (a dict): walk_host (those skeletons), paths, occurrences (the vertices on all paths), walk_s (the device calls)
+    and pack_s (the numpy around them) are added to.  No CPU fallback: HipUnavailableError without the library or an MI355X."""
+    eng = ops.engine()
+    skeletons = list(skeletons)
+    out = []
+    for part in forest.walk_batches(skeletons):
+        group = skeletons[part]
+        w = forest.walk(eng, group, stats=stats)
+        for k, s in enumerate(group):
+            paths = s.paths(return_indices=True) if w.host[k] else w.paths(k)
+            out.append(paths if return_indices else [s.vertices[p] for p in paths])
+        if stats is not None:
+            stats["paths"] = stats.get("paths", 0) + int(w.pstart.size - 1)
+            stats["occurrences"] = stats.get("occurrences", 0) + int(w.occ.size)
+    return out
+
+
 def remove_dust_many(skeletons, dust_threshold, stats=None):
     """remove_dust(skeleton, dust_threshold) for every skeleton of the list; an empty skeleton, and every skeleton
     under a zero threshold, comes back as the object it is.  The cable length of every component is summed on the device in another

@@ -30,7 +30,7 @@ def _xs_box_budget(eng, itemsize, region_bytes=0):
 
 def cross_sectional_area_chunked(dataset, skeletons, chunk_shape=(512, 512, 512), halo=64, anisotropy=(1, 1, 1), smoothing_window=1,
                                  step=1, multipass=False, repair_contacts=False, max_box_voxels=None, progress=False, timings=None,
-                                 fill_holes=False, visualize_section_planes=False, _sections=None):
+                                 fill_holes=False, visualize_section_planes=False, _sections=None, walk="host"):
     """kimimaro_amd.cross_sectional_area for a dataset that is never resident as a whole: the other half of what
     igneous does around kimimaro.  The result is DEFINED as what cross_sectional_area(whole dataset, skeletons, ...) returns, bit for
     bit in cross_sectional_area and equal in cross_sectional_area_contacts (whose bits name the faces of the DATASET), wherever a
@@ -59,20 +59,22 @@ def cross_sectional_area_chunked(dataset, skeletons, chunk_shape=(512, 512, 512)
     load_s (host: loading, upload, counting), and rounds, vertices, occurrences of the driver loop.
     _sections: a function with the signature of section.cross_sections_box that runs the boxes instead; it is handed the box as the
     host array and the labels themselves as words, and nothing here touches the GPU (the host-logic tests).  Without it there is no
-    CPU fallback: HipUnavailableError without the library or an MI355X."""
+    CPU fallback: HipUnavailableError without the library or an MI355X.
+    walk: cross_sectional_area's; "device" needs an engine (ops.engine()) whoever runs the boxes."""
     utility._xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    utility._xs_check_walk(walk)
     if fill_holes:
         raise NotImplementedError("cross_sectional_area_chunked(fill_holes=True) keeps raising at this entry point; the sections of "
                                   "filled labels of a dataset in boxes are cross_sectional_area_filled_chunked, which takes the same "
                                   "arguments and a region_store")
     return _xs_chunked("cross_sectional_area_chunked", False, None, dataset, skeletons, chunk_shape, halo, anisotropy, smoothing_window,
-                       step, multipass, repair_contacts, max_box_voxels, timings, _sections, None)
+                       step, multipass, repair_contacts, max_box_voxels, timings, _sections, None, walk)
 
 
 def cross_sectional_area_filled_chunked(dataset, skeletons, chunk_shape=(512, 512, 512), halo=64, anisotropy=(1, 1, 1),
                                         smoothing_window=1, step=1, multipass=False, repair_contacts=False, max_box_voxels=None,
                                         progress=False, timings=None, visualize_section_planes=False, region_store=None,
-                                        _sections=None, _regions=None):
+                                        _sections=None, _regions=None, walk="host"):
     """kimimaro_amd.cross_sectional_area_filled for a dataset that is never resident as a whole: the result is DEFINED
     as what cross_sectional_area_filled(whole dataset, skeletons, ...) returns -- bit for bit in cross_sectional_area, equal in
     cross_sectional_area_contacts -- wherever a box large enough could be loaded.  hole(L) is taken on the DATASET: a cavity that
@@ -93,14 +95,16 @@ def cross_sectional_area_filled_chunked(dataset, skeletons, chunk_shape=(512, 51
     seam_pairs (region_graph_chunked), enclosed_ms (the host search) and listed_ids (hole regions over all labels, provisional ids).
     _sections: a function with the signature of section.cross_sections_filled_box, handed the box and its region box as host arrays
     [x, y, z], the labels themselves as words and the lists as a host array; _regions: region_graph_chunked's.  With both nothing
-    touches the GPU (the host-logic tests).  Without them there is no CPU fallback."""
+    touches the GPU (the host-logic tests).  Without them there is no CPU fallback.
+    walk: cross_sectional_area's; "device" needs an engine (ops.engine()) whoever runs the boxes."""
     utility._xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    utility._xs_check_walk(walk)
     return _xs_chunked("cross_sectional_area_filled_chunked", True, region_store, dataset, skeletons, chunk_shape, halo, anisotropy,
-                       smoothing_window, step, multipass, repair_contacts, max_box_voxels, timings, _sections, _regions)
+                       smoothing_window, step, multipass, repair_contacts, max_box_voxels, timings, _sections, _regions, walk)
 
 
 def _xs_chunked(name, filled, region_store, dataset, skeletons, chunk_shape, halo, anisotropy, smoothing_window, step, multipass,
-                repair_contacts, max_box_voxels, timings, _sections, _regions):
+                repair_contacts, max_box_voxels, timings, _sections, _regions, walk="host"):
     """the body of cross_sectional_area_chunked and cross_sectional_area_filled_chunked (filled), after the argument checks"""
     if int(halo) != halo or int(halo) < 1:
         raise ValueError("{}: halo must be a positive integer. Got: {}".format(name, halo))
@@ -237,7 +241,9 @@ def _xs_chunked(name, filled, region_store, dataset, skeletons, chunk_shape, hal
         return launch
 
     if jobs:
-        utility._xs_run(None, None, None, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, launch_hook=hook)
+        walker = None if walk == "host" else (eng if eng is not None else ops.engine())
+        utility._xs_run(walker, None, None, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, launch_hook=hook,
+                        walk=walk)
         if not state["counted"]:                                         # (no vertex lies on a path: the counts decide -1 or 0 all the same)
             hook(np.zeros((0, 3), dtype=np.int64), np.zeros(0, dtype=np.uint32), np.zeros((0, 3)))(none)
         for (s, word, _), (area, contact) in zip(jobs, kept):           # utility.py:141-154, once the counts are known
@@ -251,4 +257,5 @@ def _xs_chunked(name, filled, region_store, dataset, skeletons, chunk_shape, hal
     if timings is not None:
         timings.update(total, kernel_ms=stats.get("kernel_ms", 0.0), rounds=stats.get("rounds", 0), vertices=stats.get("vertices", 0),
                        occurrences=stats.get("occurrences", 0))
+        timings.update({k: stats[k] for k in ("walk_host", "paths", "walk_s", "pack_s", "prepare_s") if k in stats})
     return skeletons

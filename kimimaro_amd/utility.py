@@ -13,7 +13,7 @@ import time
 
 import numpy as np
 
-from . import _abi, feature, ops, points, section
+from . import _abi, feature, forest, ops, points, section
 from .skeleton import Skeleton
 from .volume import _device_labels
 
@@ -275,9 +275,94 @@ def _xs_occurrences(skel, an, offset, shape, smoothing_window, step):
     return vox, np.concatenate(occ_vertex), np.concatenate(occ_normal)
 
 
+def _xs_voxels(skels, an, offsets):
+    """the voxel of every vertex of every skeleton, as _xs_occurrences rounds them, minus the job's offset -> int64 [V, 3], back to
+    back; one pass over the call where every skeleton holds float32 vertices"""
+    verts = [np.asarray(s.vertices).reshape(-1, 3) for s in skels]
+    counts = np.array([v.shape[0] for v in verts], dtype=np.int64)
+    shift = np.repeat(np.asarray(offsets, dtype=np.int64).reshape(-1, 3), counts, axis=0)
+    if not verts:
+        return np.zeros((0, 3), dtype=np.int64)
+    if all(v.dtype == np.float32 for v in verts):
+        v = np.concatenate(verts)
+        physical = np.repeat(np.array([s.space == "physical" for s in skels], dtype=bool), counts)
+        vox = np.round(v)
+        if physical.any():
+            vox[physical] = (v[physical] / an).round()
+        return vox.astype(np.int64) - shift
+    parts = [(v / an).round().astype(np.int64) if s.space == "physical" else np.round(v).astype(np.int64) for s, v in zip(skels, verts)]
+    return np.concatenate(parts) - shift
+
+
+def _xs_occurrences_many(eng, jobs, an, shape, smoothing_window, step, stats=None):
+    """_xs_occurrences for every job (skeleton, word, offset) of a call, the paths walked and the normals smoothed on the device
+    (forest.walk) -> per job (vox, occ_vertex, occ_normal, is_branch): the first three what _xs_occurrences(skel, an,
+    offset, shape, smoothing_window, step) returns, bit for bit (NaNs by position); is_branch bool [n], True at skel.branches().
+    Host numpy over the whole call: the rounding, canon, the keep filter, the compaction.  A skeleton with a cyclic component, or
+    with a voxel coordinate of forest.VOX_LIMIT or more, goes through _xs_occurrences whole and counts in stats["walk_host"];
+    stats also receives paths, occurrences (kept ones), walk_s and pack_s."""
+    t0 = time.perf_counter()
+    skels = [skel for skel, _, _ in jobs]
+    vox = _xs_voxels(skels, an, [offset for _, _, offset in jobs])
+    counts = np.array([np.asarray(s.vertices).reshape(-1, 3).shape[0] for s in skels], dtype=np.int64)
+    vstart = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    owner = np.repeat(np.arange(len(skels)), counts)
+    far = np.zeros(len(skels), dtype=bool)
+    if vox.size:
+        far[owner[np.abs(vox).max(axis=1) >= forest.VOX_LIMIT]] = True
+    inner = {} if stats is None else stats
+    pack0, walk0 = inner.get("pack_s", 0.0), inner.get("walk_s", 0.0)
+    w = forest.walk(eng, [Skeleton(s.vertices) if f else s for s, f in zip(skels, far)], np.where(far[owner][:, None], 0, vox), smoothing_window, inner)
+    if far.any():
+        inner["walk_host"] = inner.get("walk_host", 0) + int(far.sum())
+    # canon: the LAST vertex in a voxel, per skeleton -- the largest index of every (skeleton, voxel) group
+    order = np.lexsort((vox[:, 2], vox[:, 1], vox[:, 0], owner)) if vox.size else np.zeros(0, dtype=np.int64)
+    rows = np.concatenate([owner[order][:, None], vox[order]], axis=1)
+    tail = np.ones(order.size, dtype=bool)
+    tail[:-1] = np.any(rows[1:] != rows[:-1], axis=1)
+    group = np.cumsum(tail) - tail                                           # lexsort is stable: a group's vertices ascend
+    canon = np.empty(order.size, dtype=np.int64)
+    canon[order] = order[np.flatnonzero(tail)[group]]
+    # keep: every step-th vertex of a path and both its ends, inside the volume
+    lens = np.diff(w.pstart)
+    path_of = np.repeat(np.arange(lens.size), lens)
+    i = np.arange(w.occ.size) - w.pstart[path_of]
+    keep = ((i + 1) % step == 0) | (i == 0) | (i == lens[path_of] - 1)
+    pts = vox[w.occ]
+    keep &= np.all((pts >= 0) & (pts < np.array(shape, dtype=np.int64)), axis=1)
+    kept = np.concatenate([[0], np.cumsum(keep)])
+    cut = kept[w.pstart[w.pcut]]                                             # per skeleton: its kept occurrences
+    occ_vertex = canon[w.occ[keep]] - np.repeat(vstart[:-1], np.diff(cut))
+    occ_normal = w.normal[keep]
+    branch = w.degree >= 3
+    out, hosted = [], w.host | far
+    for k, (skel, _, offset) in enumerate(jobs):
+        a, b = vstart[k], vstart[k + 1]
+        if hosted[k]:
+            _, ov, on = _xs_occurrences(skel, an, offset, shape, smoothing_window, step)
+            is_branch = np.zeros(b - a, dtype=bool)
+            is_branch[skel.branches()] = True
+        else:
+            ov, on, is_branch = occ_vertex[cut[k]:cut[k + 1]], occ_normal[cut[k]:cut[k + 1]], branch[a:b]
+        out.append((vox[a:b], ov, on, is_branch))
+    if stats is not None:
+        stats["paths"] = stats.get("paths", 0) + int(lens.size)
+        stats["occurrences"] = int(sum(ov.size for _, ov, _, _ in out))
+        spent = (stats.get("pack_s", 0.0) - pack0) + (stats.get("walk_s", 0.0) - walk0)
+        stats["pack_s"] = stats.get("pack_s", 0.0) + (time.perf_counter() - t0) - spent
+    return out
+
+
+def _xs_check_walk(walk):
+    if walk not in ("host", "device"):
+        raise ValueError('walk must be "host" or "device". Got: %r' % (walk,))
+
+
 def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, stats, holes=None,
-            launch_hook=None):
-    """launch_hook (cross_sectional_area_chunked, kimimaro_amd.post): who evaluates the items when the volume is not resident.  Once
+            launch_hook=None, walk="host"):
+    """walk="device": the occurrences of all jobs come from _xs_occurrences_many, which needs `eng`; "host": from
+    _xs_occurrences, job by job.  The items are the same, in the same order.
+    launch_hook (cross_sectional_area_chunked, kimimaro_amd.post): who evaluates the items when the volume is not resident.  Once
     the items are laid out it is called as launch_hook(voxel int64 [m, 3], word u32 [m], normal f64 [m, 3]) -- item position k is
     the section through `voxel[k]` (in the frame of `shape`, which may hold 2^32 voxels or more) of the job word `word[k]` with
     `normal[k]` -- and returns the function from item positions (an int64 array) to (area f32, contact u8) that every round below
@@ -292,7 +377,9 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
     an64 = an.astype(np.float64)
     starts, area_parts, contact_parts, seed_parts, word_parts, branch_parts, occ_v, occ_n = [0], [], [], [], [], [], [], []
     vox_parts = []
-    for skel, word, offset in jobs:
+    _xs_check_walk(walk)
+    many = _xs_occurrences_many(eng, jobs, an, shape, smoothing_window, step, stats) if walk == "device" and jobs else None
+    for at, (skel, word, offset) in enumerate(jobs):
         nv = int(np.asarray(skel.vertices).reshape(-1, 3).shape[0])
         if repair_contacts or (multipass and hasattr(skel, "cross_sectional_area")):       # utility.py:250-255
             area_parts.append(np.array(skel.cross_sectional_area, dtype=np.float32).reshape(-1))
@@ -301,14 +388,17 @@ def _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, mu
         else:
             area_parts.append(np.zeros(nv, dtype=np.float32))
             contact_parts.append(np.zeros(nv, dtype=np.uint8))
-        vox, ov, on = _xs_occurrences(skel, an, offset, shape, smoothing_window, step)
+        if many is None:
+            vox, ov, on = _xs_occurrences(skel, an, offset, shape, smoothing_window, step)
+            is_branch = np.zeros(nv, dtype=bool)
+            is_branch[skel.branches()] = True
+        else:
+            vox, ov, on, is_branch = many[at]
         if launch_hook is None:
             seed_parts.append(section.seed_index(vox, shape))
         else:
             vox_parts.append(vox)
         word_parts.append(np.full(nv, word, dtype=np.uint32))
-        is_branch = np.zeros(nv, dtype=bool)
-        is_branch[skel.branches()] = True
         branch_parts.append(is_branch)
         occ_v.append(ov + starts[-1])
         occ_n.append(on)
@@ -401,18 +491,19 @@ def _xs_anisotropy(anisotropy):
 
 
 def cross_sectional_area_single(binimg, skel, roi=None, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
-                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None):
+                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None, walk="host"):
     """kimimaro.cross_sectional_area_single (kimimaro/utility.py:168-349): the cross sectional areas of ONE skeleton against a binary
     image of its object (foreground = non-zero; numpy, or a torch tensor on the GPU).  roi: where the image sits in the skeleton's
     voxel frame -- anything with a `.minpt`, or three numbers -- subtracted from the vertices.  Everything else as
     cross_sectional_area.  The skeleton is changed in place and returned."""
     _xs_check_arguments(step, smoothing_window, visualize_section_planes)
+    _xs_check_walk(walk)
     img = points.check_binary_image(binimg)
     eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
     d_img, shape = points.device_binary_image(eng, img)
     offset = np.zeros(3, dtype=np.int64) if roi is None else np.asarray(getattr(roi, "minpt", roi), dtype=np.int64).reshape(3)
-    _xs_run(eng, d_img, 1, shape, an, [(skel, 1, offset)], smoothing_window, step, multipass, repair_contacts, _stats)
+    _xs_run(eng, d_img, 1, shape, an, [(skel, 1, offset)], smoothing_window, step, multipass, repair_contacts, _stats, walk=walk)
     _add_property(skel, XS_PROP)
     _add_property(skel, XS_CONTACT_PROP)
     return skel
@@ -420,7 +511,7 @@ def cross_sectional_area_single(binimg, skel, roi=None, anisotropy=(1, 1, 1), sm
 
 def cross_sectional_area(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
                          fill_holes=False, multipass=False, repair_contacts=False, visualize_section_planes=False, step=1,
-                         _stats=None):
+                         _stats=None, walk="host"):
     """kimimaro.cross_sectional_area (kimimaro/utility.py:351-560): for every vertex of every skeleton the area of the section of its
     label by the plane through the vertex's voxel whose normal points to the next vertex of the path (the part of
     the plane inside the 26-connected piece of cut voxels of the label around the vertex).  Every skeleton gains
@@ -437,13 +528,17 @@ def cross_sectional_area(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_
     A skeleton is skipped when its id is 0, its label does not occur or occupies a single voxel (utility.py:141-154); a bool volume
     assigns every skeleton to label 1.  all_labels: numpy, or a torch tensor on the GPU indexed [x, y, z].
     fill_holes=True raises NotImplementedError here: cross_sectional_area_filled is that option.
-    `progress` and `in_place` are accepted and have no effect."""
+    `progress` and `in_place` are accepted and have no effect.
+    walk="device" walks the paths and smooths the normals of all skeletons on the GPU instead of skeleton by skeleton
+    in the interpreter ("host", the default); the attributes come out equal, bit for bit.  Any other value is a ValueError."""
     _xs_check_arguments(step, smoothing_window, visualize_section_planes, fill_holes)
-    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, False, multipass, repair_contacts, step, _stats)
+    _xs_check_walk(walk)
+    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, False, multipass, repair_contacts, step, _stats, walk)
 
 
 def cross_sectional_area_filled(all_labels, skeletons, anisotropy=(1, 1, 1), smoothing_window=1, progress=False, in_place=False,
-                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None):
+                                multipass=False, repair_contacts=False, visualize_section_planes=False, step=1, _stats=None,
+                                walk="host"):
     """kimimaro.cross_sectional_area(fill_holes=True): cross_sectional_area, same arguments and outputs, with one substitution.  It
     takes the sections of filled(L) = L and its holes instead of L (kimimaro/utility.py:152-162 fills every label's
     crop with fill_voids): a hole of L is a 6-connected piece of the rest of the volume that owns no voxel on a face of the volume,
@@ -454,7 +549,8 @@ def cross_sectional_area_filled(all_labels, skeletons, anisotropy=(1, 1, 1), smo
     (8 bytes x the power of two above 32 slots per region, 4 x that on a retry) and frees them before the first section.
     cross_sectional_area(fill_holes=False) allocates none of this."""
     _xs_check_arguments(step, smoothing_window, visualize_section_planes)
-    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, True, multipass, repair_contacts, step, _stats)
+    _xs_check_walk(walk)
+    return _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, True, multipass, repair_contacts, step, _stats, walk)
 
 
 def _xs_finish(skels):
@@ -468,7 +564,7 @@ def _xs_finish(skels):
             s.cross_sectional_area_contacts = np.zeros(len(s.vertices), dtype=np.uint8)
 
 
-def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, multipass, repair_contacts, step, _stats):
+def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, multipass, repair_contacts, step, _stats, walk="host"):
     """the body of cross_sectional_area and cross_sectional_area_filled, after the argument checks"""
     eng = ops.engine()                                   # raises HipUnavailableError without the library or a gfx950 device
     an = _xs_anisotropy(anisotropy)
@@ -485,6 +581,6 @@ def _xs_labels(all_labels, skeletons, anisotropy, smoothing_window, fill_holes, 
     if fill_holes and jobs:
         hole_stats = None if _stats is None else _stats.setdefault("holes", {})
         holes = section.hole_tables(eng, d_lab, label_bytes, shape, {word for _, word, _ in jobs}, hole_stats)
-    _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats, holes)
+    _xs_run(eng, d_lab, label_bytes, shape, an, jobs, smoothing_window, step, multipass, repair_contacts, _stats, holes, walk=walk)
     _xs_finish(skels)
     return skeletons

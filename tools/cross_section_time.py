@@ -3,7 +3,11 @@ made.  After a warm-up call the analysis runs several times; reported are the me
 which ends in device-to-host copies), of the kernel time (HIP events around the launches) and of the host driver's parts (path
 walking and batching before the first launch, the first launch with its copies, the follow-up rounds), and vertices per second.
 
-    python tools/cross_section_time.py [c3] [runs] [--fill-holes]
+    python tools/cross_section_time.py [c3] [runs] [--fill-holes] [--walk host|device]
+
+--walk device walks the paths and smooths the normals on the GPU (default host): prepare_s, the host driver's time
+before the first launch, is printed next to the wall time and the kernel time, with walk_s (the walk's device calls and copies)
+and pack_s (the numpy around them) where the device walks, and a checksum of the areas to compare two runs by.
 
 --fill-holes times cross_sectional_area_filled (the reference's fill_holes=True): also reported are what Engine.region_graph says (regions, pairs, the passes' milliseconds), the
 host search's milliseconds (kh_host_enclosed_regions), the size of the lists and the number of labels with holes.
@@ -43,8 +47,14 @@ def shells_volume(device):
     return torch.from_numpy(lab.transpose(2, 1, 0).copy()).to(device).permute(2, 1, 0), (1, 1, 1), skels
 
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-fill_holes = "--fill-holes" in sys.argv[1:]
+argv = sys.argv[1:]
+walk = "host"
+if "--walk" in argv:
+    at = argv.index("--walk")
+    walk = argv[at + 1]
+    del argv[at:at + 2]
+args = [a for a in argv if not a.startswith("--")]
+fill_holes = "--fill-holes" in argv
 name = args[0] if len(args) > 0 else "c3"
 runs = int(args[1]) if len(args) > 1 else 5
 eng = Engine()
@@ -62,13 +72,13 @@ nvert = sum(len(s.vertices) for s in skels.values())
 
 def timed(fill):
     run = kimimaro_amd.cross_sectional_area_filled if fill else kimimaro_amd.cross_sectional_area
-    run(lab, skels, anisotropy=an)  # warm-up (allocator, code objects)
+    run(lab, skels, anisotropy=an, walk=walk)  # warm-up (allocator, code objects)
     out = []
     for _ in range(runs):
         stats = {}
         eng.sync()
         t0 = time.perf_counter()
-        run(lab, skels, anisotropy=an, _stats=stats)
+        run(lab, skels, anisotropy=an, _stats=stats, walk=walk)
         stats["wall_s"] = time.perf_counter() - t0
         out.append(stats)
     return out
@@ -88,7 +98,19 @@ print("  median of %d runs: wall %.1f ms = %.0f vertices/s; kernel %.2f ms (%.1f
 print("  host driver: paths and batching %.1f ms, first launch with copies %.1f ms, follow-up rounds and means %.1f ms; spread of the "
       "wall %.1f .. %.1f ms" % (med("prepare_s") * 1e3, med("first_launch_s") * 1e3, med("finish_s") * 1e3,
                                 min(r["wall_s"] for r in rows) * 1e3, max(r["wall_s"] for r in rows) * 1e3))
-result = {"workload": name, "fill_holes": fill_holes, "skeletons": len(skels), "vertices": nvert, "items": last["items"],
+import hashlib
+import numpy as np
+digest = hashlib.sha256(b"".join(np.ascontiguousarray(s.cross_sectional_area).tobytes() + np.ascontiguousarray(s.cross_sectional_area_contacts).tobytes()
+                                 for s in skels.values())).hexdigest()[:16]
+spread = lambda key: (min(r[key] for r in rows) * 1e3, max(r[key] for r in rows) * 1e3)
+print("  walk=%s: wall %.1f ms, prepare_s %.1f ms (%.1f .. %.1f), kernel %.2f ms; walk_s %.1f ms, pack_s %.1f ms, %d paths, %d skeletons walked by "
+      "the host; areas and contacts sha256 %s" % ((walk, wall * 1e3, med("prepare_s") * 1e3) + spread("prepare_s") + (
+          kernel_ms, statistics.median(r.get("walk_s", 0.0) for r in rows) * 1e3, statistics.median(r.get("pack_s", 0.0) for r in rows) * 1e3,
+          last.get("paths", 0), last.get("walk_host", 0), digest)))
+result = {"workload": name, "walk": walk, "areas_sha256": digest, "walk_s": statistics.median(r.get("walk_s", 0.0) for r in rows),
+          "pack_s": statistics.median(r.get("pack_s", 0.0) for r in rows), "wall_min_s": min(r["wall_s"] for r in rows),
+          "wall_max_s": max(r["wall_s"] for r in rows), "prepare_min_s": min(r["prepare_s"] for r in rows),
+          "prepare_max_s": max(r["prepare_s"] for r in rows), "occurrences": last["occurrences"], "fill_holes": fill_holes, "skeletons": len(skels), "vertices": nvert, "items": last["items"],
           "rounds": last["rounds"], "wall_s": wall, "kernel_ms": kernel_ms, "prepare_s": med("prepare_s"),
           "first_launch_s": med("first_launch_s"), "finish_s": med("finish_s"), "vertices_per_s": nvert / wall, "waves": last["waves"]}
 if fill_holes:
